@@ -9,7 +9,11 @@ reference's training loop (one flat RCCL all-reduce of the segmentation-head gra
 ~0.82 MB for ViT-S).  Inputs are synthetic, resident in HBM before the timed region; a ring
 of input sets larger than the 256 MB Infinity Cache is rotated so steps read from HBM.
 
-    python bench.py --gpus 1 --steps 50 --warmup 10
+A plain run sets up, warms up, times the K steps and prints the headline record (the measurements beside it are null);
+--full adds the other precision mode, the forward / backward split, the product path, the rooflines and the CPU baseline.
+--dump-outputs DIR writes what the last timed step returned, for comparing two builds on the same seeded inputs.
+
+    python bench.py --gpus 1 --steps 50 --warmup 10 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -81,6 +85,26 @@ def head_grad_numel(C, K, n_classes=27):
     """Trainable parameters whose gradients DDP all-reduces:
     cluster1 (C*K+K), cluster2 (C*C+C + C*K+K), linear_probe (K*n+n), cluster_probe (n*K)."""
     return (C * K + K) + (C * C + C + C * K + K) + (K * n_classes + n_classes) + n_classes * K
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path, arrays):
+    """name -> tensor as path/<name>.npy, float32, in the logical shape a caller sees.  Beyond DUMP_LIMIT_BYTES in all (B = 32 cfg-2:
+    37 MB, whole), every array becomes the same fraction of its flattened elements, at the sorted positions of a seed-0 draw."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES - 1024 * len(arrays)          # (room for the .npy headers)
+    total = 4 * sum(t.numel() for t in arrays.values())
+    frac = min(1.0, budget / total) if total else 1.0
+    rng = np.random.default_rng(0)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if frac < 1.0:
+            flat = a.reshape(-1)
+            a = flat[np.sort(rng.choice(flat.size, int(flat.size * frac), replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def make_inputs(B, C, H, W, K, S, n_neg, seed, dev, layout="cl"):
@@ -334,12 +358,24 @@ def main():
                          "the record says so and carries no throughput claim")
     ap.add_argument("--layout", default="cl", choices=["cl", "nchw"],
                     help="cl = channels-last strided views as DinoFeaturizer emits (default); nchw = contiguous NCHW")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: the other precision mode, the forward / backward split, the product path, "
+                         "feature_samples = 16, B = 16, the per-step distribution, the rooflines (rocprofv3 counter passes, traffic skeleton), "
+                         "the CPU baseline and, with a process group, every rank's time and the all-reduce alone.  Without it a run sets up, "
+                         "warms up, times the K steps and prints the headline (--no-alt / --no-cpu-baseline / --traffic act under --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (loss means, intra / inter / negative cd, negative "
+                         "loss, d_code, d_code_pos) as DIR/<name>.npy in float32 (rank 0; a fixed seeded sample beyond %d MB in all)"
+                         % (DUMP_LIMIT_BYTES // 10 ** 6))
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     dry = args.dry_run_cpu
+    full = args.full
+    if dry and args.dump_outputs:
+        ap.error("--dump-outputs needs the kernels: not with --dry-run-cpu")
     if dry:
         dev = torch.device("cpu")
     else:
@@ -394,6 +430,7 @@ def main():
             torch.cuda.synchronize()
 
     last_local = [0.0]                       # this rank's own seconds of the last timed_run (before the MAX over ranks)
+    last_step = [None]                       # what the last step of the last timed_run returned: (forward outputs, gradients)
 
     def timed_run(precision, steps, warmup, fwd_only=args.fwd_only, collective=True, use_graph=True):
         """W untimed + K timed steps of the whole job in one precision mode; returns (seconds, launch mode, desc)."""
@@ -424,6 +461,7 @@ def main():
                 keep[i] = (out, grads)
             else:
                 keep[i] = (out,)
+            return keep[i]
 
         if not dry:
             step_compute = step_compute_gpu
@@ -443,12 +481,13 @@ def main():
                 # real training step amortises over its backbone forward; K steps are always exactly K steps of work.
                 spg = args.steps_per_graph or args.sets
                 graphs = []
+                graph_last = []                     # per graph: the tensors its last captured step writes on every replay
                 for g0 in range(0, args.sets * spg, spg):
                     gr = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(gr, capture_error_mode="thread_local"):     # RCCL's watchdog thread must not break a capture
                         prev = None
                         for j in range(spg):
-                            step_compute((g0 + j) % args.sets)
+                            res = step_compute((g0 + j) % args.sets)
                             if coll_in_graph:
                                 # step j's all-reduce runs on RCCL's stream under step j + 1's kernels (as it runs under the next
                                 # backbone forward in training); the graph joins the last one before it ends
@@ -458,13 +497,15 @@ def main():
                         if prev is not None:
                             prev.wait()
                     graphs.append(gr)
+                    graph_last.append(res)
                     if spg % args.sets == 0:
                         break                       # every replay covers whole rotations: one graph is enough
                 single = []
+                single_out = []
                 for i in range(args.sets):          # single-step graphs for the remainder of K
                     gr = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(gr, capture_error_mode="thread_local"):
-                        step_compute(i)
+                        single_out.append(step_compute(i))
                         if coll_in_graph:
                             reducer.allreduce_mean(async_op=False, single_rank_ok=True)
                     single.append(gr)
@@ -488,8 +529,9 @@ def main():
             i = k % args.sets
             if graphs is not None:
                 single[i].replay()
+                last_step[0] = single_out[i]
             else:
-                step_compute(i)
+                last_step[0] = step_compute(i)
             do_collective()
 
         def do_collective():
@@ -508,6 +550,7 @@ def main():
                 r = 0
                 while n - k >= spg:
                     graphs[r % len(graphs)].replay()
+                    last_step[0] = graph_last[r % len(graphs)]
                     r += 1
                     for _ in range(spg):
                         do_collective()
@@ -555,9 +598,16 @@ def main():
         mode = "graph" if trial["graph"] < trial["eager"] else "eager"
     dt, launch, desc = timed_run(args.precision, args.steps, args.warmup, use_graph=(mode == "graph"))
     dt_local = last_local[0]
+    if args.dump_outputs and rank == 0:
+        fwd_out, *grads = last_step[0]
+        arrays = dict(zip(("loss_means", "intra_cd", "inter_cd", "neg_loss", "neg_cd"), fwd_out[:5]))
+        if grads:
+            arrays.update(d_code=grads[0][0], d_code_pos=grads[0][1])
+        dump_outputs(args.dump_outputs, {k: v for k, v in arrays.items() if v is not None})
+    last_step[0] = None
     use_graph = mode == "graph"
     alt = None
-    if not args.no_alt:                     # the other arithmetic mode, shorter, for the record (all ranks take part)
+    if full and not args.no_alt:            # the other arithmetic mode, shorter, for the record (all ranks take part)
         other = "f32" if args.precision == "f16x3" else "f16x3"
         steps_alt = max(20, args.steps // 4)
         dt_alt, _, desc_alt = timed_run(other, steps_alt, max(4, args.warmup // 4), use_graph=use_graph)
@@ -566,7 +616,7 @@ def main():
 
     # ---- the forward alone (same graphs without the backward): the backward's share is the difference
     split = None
-    if not args.fwd_only and not args.no_alt and not dry:
+    if full and not args.fwd_only and not args.no_alt and not dry:
         steps_f = max(20, args.steps // 4)
         dt_f, _, _ = timed_run(args.precision, steps_f, max(4, args.warmup // 4), fwd_only=True, collective=False, use_graph=use_graph)
         split = {"forward_ms": dt_f / steps_f * 1e3, "backward_ms": dt / args.steps * 1e3 - dt_f / steps_f * 1e3, "steps": steps_f}
@@ -574,13 +624,13 @@ def main():
     # ---- the product path: ContrastiveCorrelationLoss(cfg)(...) + .backward() exactly as a training step calls it
     # (train_segmentation.py:163-181): RNG draws, autograd.Function, weighted sum, backward - eager and graph-replayed
     product = None
-    if rank == 0 and not args.no_alt and not dry:
+    if rank == 0 and full and not args.no_alt and not dry:
         product = product_path(sets, cfg, args, dt / args.steps)
 
     # ---- the other native path, for the record: cfg.feature_samples = 16 (256 points per image: 8 + 4 launches of csrc/corr_wide.hip behind the
     # same two C-ABI calls), one input set, eager launches (the host needs ~0.16 ms per step, the kernels ~0.36)
     wide = None
-    if rank == 0 and not args.no_alt and not dry and S <= 11 and not args.fwd_only:
+    if rank == 0 and full and not args.no_alt and not dry and S <= 11 and not args.fwd_only:
         try:
             S16 = 16
             cfg16 = Cfg()
@@ -621,7 +671,7 @@ def main():
     # too): the same workload at B = 16 - since round 6 the column-half launch (csrc/corr_fused_half.hip) -, four rotating input sets, eager
     # launches; the forward by HIP events around single launches like the headline's, the full-tile launch of the same library beside it
     ref16 = None
-    if rank == 0 and not args.no_alt and not dry and S == 11 and B == 32 and not args.fwd_only:
+    if rank == 0 and full and not args.no_alt and not dry and S == 11 and B == 32 and not args.fwd_only:
         try:
             B16 = 16
             sets16 = [make_inputs(B16, C, H, W, K, S, n_neg, 5000 + i, dev, args.layout) for i in range(4)]
@@ -714,7 +764,7 @@ def main():
     # ---- per-step distribution (outside the timed region): one HIP event behind every eagerly launched step on torch's current
     # stream - the stream capi launches on -, consecutive differences = what each step took incl. its launch gaps
     step_dist = None
-    if rank == 0 and not dry:
+    if rank == 0 and full and not dry:
         try:
             prec_ = capi.PREC_F32 if args.precision == "f32" else capi.PREC_F16X3
             desc_d = capi.make_desc(B, C, K, H, W, S, n_neg, cfg, (cfg.pos_intra_shift, cfg.pos_inter_shift, cfg.neg_inter_shift), prec_)
@@ -745,7 +795,7 @@ def main():
         except Exception as e:       # noqa: BLE001 - a record for the reader, never the reason a bench run fails
             step_dist = {"error": "%s: %s" % (type(e).__name__, e)}
 
-    if rank == 0 and not dry:
+    if rank == 0 and full and not dry:
         ms_samp, ms_main, ms_fin = forward_launch_ms(desc)
         ab = algorithmic_bytes_fwd(B, C, H, W, K, S, n_neg)
         fl = algorithmic_flops_fwd(B, C, K, S, n_neg)
@@ -867,7 +917,7 @@ def main():
                             algorithmic_bytes=abb, us=tb * 1e6)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and full and not args.no_cpu_baseline:
         cpu = cpu_baseline(B, C, H, W, K, S, n_neg, cfg)
 
     check = None
@@ -879,7 +929,7 @@ def main():
         alt.pop("desc", None)
     # ---- N > 1 (and --force-collective): what each rank saw, and the gradient all-reduce on its own, so that a scaling run explains itself
     coll_stats = None
-    if dist is not None:
+    if dist is not None and full:
         per_rank = torch.zeros(world, device=dev, dtype=torch.float64)
         per_rank[rank] = dt_local / args.steps * 1e3
         dist.all_reduce(per_rank)

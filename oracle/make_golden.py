@@ -291,12 +291,31 @@ def wide_cases(M):
              dino_like=True, channels_last=True)
 
 
+def salience_case(M):
+    """sample_nonzero_locations (modules.py:298-311) on the salience maps of tests/test_host_logic.py's salience test, after
+    torch.manual_seed(11): the coordinates the reference draws, so that the test needs no reference sources.
+    `python oracle/make_golden.py salience` writes only this file."""
+    g = torch.Generator().manual_seed(3)
+    B, H = 3, 12
+    sal = (torch.rand(B, H, H, generator=g) > 0.7).float()
+    sal[1] = 0
+    sal_pos = (torch.rand(B, H, H, generator=g) > 0.5).float()
+    shape = [B, 5, 5, 2]
+    torch.manual_seed(11)
+    n1 = M.sample_nonzero_locations(sal, shape)
+    n2 = M.sample_nonzero_locations(sal_pos, shape)
+    np.savez_compressed(os.path.join(OUT, "salience_coords.npz"), sal=sal.numpy(), sal_pos=sal_pos.numpy(), n1=n1.numpy(), n2=n2.numpy())
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
     M = ref_shim.load_reference_modules()
     if sys.argv[1:] == ["wide"]:
         wide_cases(M)
+        return
+    if sys.argv[1:] == ["salience"]:
+        salience_case(M)
         return
     primitives_case(M)
     seeded_e2e_case(M)
@@ -320,6 +339,7 @@ def main():
              store_inputs=False, subsample=61, dino_like=True, channels_last=True)
     # BASELINE config-4 shape (ViT-B/8 320^2 -> 768 x 40 x 40), B=2 to stay small
     wide_cases(M)
+    salience_case(M)
     run_case(M, "cfg4_B2_vitb8", B=2, C=768, H=40, W=40, K=70, S=11, n_neg=5, seed=13,
              store_inputs=False, subsample=61)
 

@@ -264,10 +264,10 @@ def test_allreduce_does_not_touch_the_library_state():
 # ------------------------------------------------------------------ salience-guided coordinates (cfg.use_salience)
 def test_salience_coords_follow_the_reference_draw_order():
     """modules.py:355-365 + sample_nonzero_locations :298-311: per image one randint over its non-zero salience pixels
-    (or over the whole map if there are none), then rand, rand, rand(mask) - same generator, same order.  When the
-    reference sources are present (build container) the imported reference function is the comparison, otherwise the
-    expected values are restated from those lines."""
-    from oracle import ref_shim
+    (or over the whole map if there are none), then rand, rand, rand(mask) - same generator, same order.  The expected
+    values are restated from those lines; the restatement's draws equal what the reference function drew on the same maps
+    after the same seed (tests/golden/salience_coords.npz, oracle/make_golden.py: salience_case)."""
+    gold = load_golden("salience_coords")
     cfg = _cfg()
     cfg.use_salience = True
     cfg.feature_samples = 5
@@ -276,6 +276,7 @@ def test_salience_coords_follow_the_reference_draw_order():
     sal = (torch.rand(B, H, H, generator=g) > 0.7).float()
     sal[1] = 0                                                   # an image without salient pixels: uniform randint fallback
     sal_pos = (torch.rand(B, H, H, generator=g) > 0.5).float()
+    assert np.array_equal(sal.numpy(), gold["sal"]) and np.array_equal(sal_pos.numpy(), gold["sal_pos"])
     feats = torch.zeros(B, 4, 6, 6)
     loss = M.ContrastiveCorrelationLoss(cfg)
 
@@ -285,19 +286,17 @@ def test_salience_coords_follow_the_reference_draw_order():
 
     torch.manual_seed(11)
     shape = [B, 5, 5, 2]
-    if ref_shim.available():
-        snl = ref_shim.load_reference_modules().sample_nonzero_locations
-    else:
-        def snl(t, target_size):                                 # restatement of :298-311
-            nz = torch.nonzero(t)
-            coords = torch.zeros(target_size, dtype=nz.dtype)
-            n = target_size[1] * target_size[2]
-            for i in range(t.shape[0]):
-                sel = nz[nz[:, 0] == i]
-                pick = torch.randint(t.shape[1], size=(n, 2)) if sel.shape[0] == 0 else sel[torch.randint(len(sel), size=(n,)), 1:]
-                coords[i] = pick.reshape(target_size[1], target_size[2], 2)
-            return torch.flip(coords.to(torch.float32) / t.shape[1] * 2 - 1, dims=[-1])
+    def snl(t, target_size):                                     # restatement of :298-311
+        nz = torch.nonzero(t)
+        coords = torch.zeros(target_size, dtype=nz.dtype)
+        n = target_size[1] * target_size[2]
+        for i in range(t.shape[0]):
+            sel = nz[nz[:, 0] == i]
+            pick = torch.randint(t.shape[1], size=(n, 2)) if sel.shape[0] == 0 else sel[torch.randint(len(sel), size=(n,)), 1:]
+            coords[i] = pick.reshape(target_size[1], target_size[2], 2)
+        return torch.flip(coords.to(torch.float32) / t.shape[1] * 2 - 1, dims=[-1])
     n1, n2 = snl(sal, shape), snl(sal_pos, shape)
+    assert np.array_equal(n1.numpy(), gold["n1"]) and np.array_equal(n2.numpy(), gold["n2"])
     r1 = torch.rand(shape) * 2 - 1
     r2 = torch.rand(shape) * 2 - 1
     mask = (torch.rand(shape[:-1]) > .1).unsqueeze(-1).to(torch.float32)

@@ -6,6 +6,6 @@ R=$1; shift
 for i in $(seq $R); do
   for v in "$@"; do
     cp $L/$v $L/libstego_corr.so
-    timeout 200 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-alt 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$v', round(1e3*d['ms_per_step'],2), d['roofline']['us_per_launch'], d['forward_backward_split'])"
+    timeout 200 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-alt 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$v', round(1e3*d['ms_per_step'],2), d['roofline']['us_per_launch'], d['forward_backward_split'])"
   done
 done

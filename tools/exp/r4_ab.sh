@@ -9,7 +9,7 @@ cp $L/libstego_corr.so $L/_keep.so
 for i in $(seq $R); do
   for v in "$@"; do
     cp $L/$v.so $L/libstego_corr.so
-    timeout 200 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-alt ${B:+--batch $B} 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$v', 'step', round(1e3*d['ms_per_step'],2), 'fwd', round(d['roofline']['us_per_launch']['corr_fused_kernel'],2))" >> $O/ab.txt 2>&1
+    timeout 200 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-alt ${B:+--batch $B} 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$v', 'step', round(1e3*d['ms_per_step'],2), 'fwd', round(d['roofline']['us_per_launch']['corr_fused_kernel'],2))" >> $O/ab.txt 2>&1
   done
 done
 if [ "${STAMPS:-1}" != "0" ]; then

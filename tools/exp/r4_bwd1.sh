@@ -6,8 +6,8 @@ mkdir -p $O
 timeout 900 python -m pytest tests/test_bwd_fused.py -x -q -m gpu 2>&1 | tail -15 > $O/test_bwd_fused.txt
 timeout 120 python tools/stamps_bwd_lists.py > $O/stamps_bwd_fused.txt 2>&1
 timeout 120 python tools/stamps_bwd_lists.py 16 > $O/stamps_bwd_fused_B16.txt 2>&1
-STEGO_DEBUG_BWD=1024 timeout 200 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-alt > $O/bench_two_launch.json 2> $O/bench.err
-timeout 200 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-alt > $O/bench.json 2>> $O/bench.err
+STEGO_DEBUG_BWD=1024 timeout 200 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-alt > $O/bench_two_launch.json 2> $O/bench.err
+timeout 200 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-alt > $O/bench.json 2>> $O/bench.err
 timeout 900 python -m pytest tests/test_parity_gpu.py -x -q -m gpu -k "golden or full_size or edge or border or linear or above_72 or rounds_of_whole or training_loop or loss_curve or randomised or cpp_autograd or stress or determin" 2>&1 | tail -8 > $O/test_parity_subset.txt
 cat $O/test_bwd_fused.txt $O/stamps_bwd_fused.txt $O/stamps_bwd_fused_B16.txt $O/test_parity_subset.txt
 python - <<'PY'

@@ -5,7 +5,7 @@ O=gpurun_out/${OUT:-r4_bwd4}
 mkdir -p $O
 for rep in 1 2 3; do
 for v in "$@"; do
-  STEGO_DEBUG_BWD=$v timeout 200 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-alt ${B:+--batch $B} 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('debug_bwd=$v', 'step', round(1e3*d['ms_per_step'],2), 'fwd', round(d['roofline']['us_per_launch']['corr_fused_kernel'],2))" >> $O/ab.txt 2>&1
+  STEGO_DEBUG_BWD=$v timeout 200 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-alt ${B:+--batch $B} 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('debug_bwd=$v', 'step', round(1e3*d['ms_per_step'],2), 'fwd', round(d['roofline']['us_per_launch']['corr_fused_kernel'],2))" >> $O/ab.txt 2>&1
 done
 done
 for v in "$@"; do

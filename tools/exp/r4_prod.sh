@@ -3,7 +3,7 @@ export TMPDIR=/tmp
 O=gpurun_out/r4_prod
 mkdir -p $O
 timeout 900 python -m pytest tests/test_parity_gpu.py -x -q -m gpu -k "lazy_loss or on_device_rng or training_loop or loss_curve or total_api or cpp_autograd or without_the_torch_glue or captured_product" 2>&1 | tail -5 > $O/tests.txt
-timeout 600 python bench.py --steps 200 --warmup 20 --no-cpu-baseline > $O/bench.json 2> $O/bench.err
+timeout 600 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline > $O/bench.json 2> $O/bench.err
 cat $O/tests.txt
 python - <<'PY'
 import json

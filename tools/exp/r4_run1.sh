@@ -9,6 +9,6 @@ cp $L/tl.so $L/libstego_corr.so
 timeout 120 python tools/timeline_fused.py > $O/timeline.txt 2>&1
 cp $L/base.so $L/libstego_corr.so
 timeout 120 python tools/stamps_fused.py > $O/stamps.txt 2>&1
-timeout 200 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-alt > $O/bench.json 2> $O/bench.err
-timeout 200 python bench.py --steps 200 --warmup 20 --batch 16 --no-cpu-baseline --no-alt > $O/bench_B16.json 2>> $O/bench.err
+timeout 200 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-alt > $O/bench.json 2> $O/bench.err
+timeout 200 python bench.py --full --steps 200 --warmup 20 --batch 16 --no-cpu-baseline --no-alt > $O/bench_B16.json 2>> $O/bench.err
 rocm-smi --showclocks --showperflevel > $O/smi.txt 2>&1

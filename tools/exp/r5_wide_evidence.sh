@@ -5,9 +5,9 @@ TAG=${1:-r05g}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-python bench.py --steps 100 --warmup 20 --feature-samples 16 --no-cpu-baseline --no-alt > $OUT/bench_S16.json 2> $OUT/err.txt
-python bench.py --steps 100 --warmup 20 --feature-samples 12 --no-cpu-baseline --no-alt > $OUT/bench_S12.json 2>> $OUT/err.txt
-python bench.py --steps 100 --warmup 20 --feature-samples 16 --batch 16 --no-cpu-baseline --no-alt > $OUT/bench_S16_B16.json 2>> $OUT/err.txt
+python bench.py --full --steps 100 --warmup 20 --feature-samples 16 --no-cpu-baseline --no-alt > $OUT/bench_S16.json 2> $OUT/err.txt
+python bench.py --full --steps 100 --warmup 20 --feature-samples 12 --no-cpu-baseline --no-alt > $OUT/bench_S12.json 2>> $OUT/err.txt
+python bench.py --full --steps 100 --warmup 20 --feature-samples 16 --batch 16 --no-cpu-baseline --no-alt > $OUT/bench_S16_B16.json 2>> $OUT/err.txt
 for S in 16 12; do
   bash tools/exp/r5_generic_prof.sh $S > /dev/null 2>&1
   cp gpurun_out/r5_gen_$S/kernel_stats.txt $OUT/kernel_stats_S$S.txt

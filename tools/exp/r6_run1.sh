@@ -7,6 +7,6 @@ mkdir -p $OUT
 tools/ubench/bin/fused_skeleton 32 384 28 40 > $OUT/skeleton_B32.txt 2>&1
 tools/ubench/bin/fused_skeleton 16 384 28 40 > $OUT/skeleton_B16.txt 2>&1
 tools/ubench/bin/fused_skeleton 32 768 40 30 > $OUT/skeleton_cfg4.txt 2>&1
-python bench.py --steps 200 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --steps 200 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err
 tail -c 600 $OUT/bench.err
 cat $OUT/skeleton_B32.txt

@@ -3,10 +3,10 @@
 export TMPDIR=/tmp
 OUT=gpurun_out/${1:-r06c}
 mkdir -p $OUT
-python bench.py --steps 200 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err
-python bench.py --steps 200 --warmup 20 --batch 16 --no-cpu-baseline --no-alt > $OUT/bench_B16.json 2>> $OUT/bench.err
-python bench.py --steps 100 --warmup 20 --workload vitb8_320 --batch 16 --no-cpu-baseline --no-alt > $OUT/bench_cfg4_vitb8_320_B16.json 2>> $OUT/bench.err
-python bench.py --steps 100 --warmup 20 --batch 8 --no-cpu-baseline --no-alt > $OUT/bench_B8.json 2>> $OUT/bench.err
+python bench.py --full --steps 200 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --steps 200 --warmup 20 --batch 16 --no-cpu-baseline --no-alt > $OUT/bench_B16.json 2>> $OUT/bench.err
+python bench.py --full --steps 100 --warmup 20 --workload vitb8_320 --batch 16 --no-cpu-baseline --no-alt > $OUT/bench_cfg4_vitb8_320_B16.json 2>> $OUT/bench.err
+python bench.py --full --steps 100 --warmup 20 --batch 8 --no-cpu-baseline --no-alt > $OUT/bench_B8.json 2>> $OUT/bench.err
 tail -c 400 $OUT/bench.err
 python - <<PY
 import json, glob

@@ -6,13 +6,13 @@ TAG=${1:-r04}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 (rocm-smi --showclocks --showperflevel; rocminfo | grep -i -E "compute unit|partition" | head -8) > $OUT/box.txt 2>&1
-python bench.py --steps 200 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err
-python bench.py --steps 200 --warmup 20 --batch 16 --no-cpu-baseline --no-alt > $OUT/bench_B16.json 2>> $OUT/bench.err
-python bench.py --steps 100 --warmup 20 --batch 64 --no-cpu-baseline --no-alt > $OUT/bench_B64.json 2>> $OUT/bench.err
-python bench.py --steps 100 --warmup 20 --workload vitb8_320 --no-cpu-baseline --no-alt > $OUT/bench_cfg4_vitb8_320.json 2>> $OUT/bench.err
-python bench.py --steps 100 --warmup 20 --workload vitb8_320 --batch 16 --no-cpu-baseline --no-alt > $OUT/bench_cfg4_vitb8_320_B16.json 2>> $OUT/bench.err
-python bench.py --steps 200 --warmup 20 --precision f32 --no-cpu-baseline --no-alt > $OUT/bench_f32.json 2>> $OUT/bench.err
-rocprofv3 --kernel-trace --stats -d $OUT/ks -o ks -- python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-alt --launch eager > $OUT/ks_bench.json 2> $OUT/ks.err
+python bench.py --full --steps 200 --warmup 20 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --steps 200 --warmup 20 --batch 16 --no-cpu-baseline --no-alt > $OUT/bench_B16.json 2>> $OUT/bench.err
+python bench.py --full --steps 100 --warmup 20 --batch 64 --no-cpu-baseline --no-alt > $OUT/bench_B64.json 2>> $OUT/bench.err
+python bench.py --full --steps 100 --warmup 20 --workload vitb8_320 --no-cpu-baseline --no-alt > $OUT/bench_cfg4_vitb8_320.json 2>> $OUT/bench.err
+python bench.py --full --steps 100 --warmup 20 --workload vitb8_320 --batch 16 --no-cpu-baseline --no-alt > $OUT/bench_cfg4_vitb8_320_B16.json 2>> $OUT/bench.err
+python bench.py --full --steps 200 --warmup 20 --precision f32 --no-cpu-baseline --no-alt > $OUT/bench_f32.json 2>> $OUT/bench.err
+rocprofv3 --kernel-trace --stats -d $OUT/ks -o ks -- python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-alt --launch eager > $OUT/ks_bench.json 2> $OUT/ks.err
 python tools/rocpd_stats.py $OUT/ks/ks_results.db > $OUT/kernel_stats.txt 2>&1
 bash tools/exp/pmc_fused.sh $OUT/pmc > /dev/null 2>&1
 cp $OUT/pmc/summary.txt $OUT/pmc_summary.txt
