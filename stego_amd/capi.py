@@ -47,6 +47,15 @@ class StegoHeadDesc(Structure):
                 ("tok_stride", c_int64), ("img_stride", c_int64), ("tokens_amax", c_void_p)]
 
 
+class StegoCrfDesc(Structure):
+    """include/stego_crf.h"""
+    _fields_ = [("B", c_int32), ("C", c_int32), ("H", c_int32), ("W", c_int32), ("n_iter", c_int32), ("pos_w", c_float),
+                ("pos_xy_std", c_float), ("bi_w", c_float), ("bi_xy_std", c_float), ("bi_rgb_std", c_float)]
+
+
+CRF_ERR_LIMITS, CRF_ERR_RANGE = 20, 21
+
+
 _H = POINTER(StegoHeadDesc)
 _D = POINTER(StegoCorrDesc)
 _M = POINTER(StegoMap)
@@ -61,6 +70,9 @@ SIGNATURES = {
     "stego_head_bwd_workspace_bytes": (c_size_t, [_H]),
     "stego_head_fwd": (c_int32, [_H] + [_P] * 10 + [_P] * 3 + [_P, c_size_t, _P]),
     "stego_head_bwd": (c_int32, [_H] + [_P] * 6 + [_P] * 6 + [_P, c_size_t, _P]),
+    "stego_crf_workspace_bytes": (c_size_t, [POINTER(StegoCrfDesc)]),
+    "stego_crf_run": (c_int32, [POINTER(StegoCrfDesc), _P, _P, _P, _P, c_size_t, _P]),
+    "stego_crf_lattice_info": (c_int32, [POINTER(StegoCrfDesc), _P, c_size_t, c_int32, c_int32, POINTER(c_int32), _P, c_int32, _P]),
     "stego_abi_version": (c_int32, []),
     "stego_debug_set": (c_int32, [c_int32, c_int32]),
     "stego_debug_occupy": (c_int32, [c_int32, c_int32, c_int32, _P]),
@@ -859,3 +871,40 @@ def head_bwd(tokens, masks, saved_h, w22, d_code, K):
         _check(lib.stego_head_bwd(byref(d), _ptr(tokens), _ptr(m1), _ptr(m2), _ptr(saved_h), _ptr(w22), _ptr(d_code),
                                   _ptr(dw1), _ptr(db1), _ptr(dw21), _ptr(db21), _ptr(dw22), _ptr(db22), _ptr(ws), ws.numel(), _stream()))
     return dw1, db1, dw21, db21, dw22, db22
+
+
+def crf_desc(B, C, H, W, n_iter, pos_w, pos_xy_std, bi_w, bi_xy_std, bi_rgb_std):
+    return StegoCrfDesc(int(B), int(C), int(H), int(W), int(n_iter), float(pos_w), float(pos_xy_std), float(bi_w), float(bi_xy_std),
+                        float(bi_rgb_std))
+
+
+def crf_workspace_bytes(desc):
+    """stego_crf_workspace_bytes (host only; 0 = invalid descriptor)."""
+    return int(load().stego_crf_workspace_bytes(byref(desc)))
+
+
+def crf_run(desc, bgr_u8, probs, keep_workspace=False, workspace=None):
+    """stego_crf_run: bgr_u8 [B,H,W,3] uint8 and probs [B,C,H,W] float32, contiguous on one HIP device -> Q [B,C,H,W] float32
+    (and the workspace, for crf_lattice_info, with keep_workspace).  `workspace`: a uint8 device tensor of at least
+    crf_workspace_bytes(desc) bytes to use instead of a fresh one."""
+    _require_dev(bgr_u8, probs)
+    lib = load()
+    dev = probs.device
+    q = torch.empty(tuple(probs.shape), dtype=torch.float32, device=dev)
+    ws = workspace if workspace is not None else _empty_bytes(max(int(lib.stego_crf_workspace_bytes(byref(desc))), 256), dev)
+    nbytes = ws.numel()
+    with _on_device(dev):
+        _check(lib.stego_crf_run(byref(desc), _ptr(bgr_u8), _ptr(probs), _ptr(q), _ptr(ws), nbytes, _stream()))
+    return (q, ws) if keep_workspace else q
+
+
+def crf_lattice_info(desc, ws, b, which, max_keys=0):
+    """(vertex count, the first max_keys packed vertex keys as uint64 numpy) of lattice `which` (0 Gaussian, 1 bilateral) of image b."""
+    import numpy as np
+    lib = load()
+    n = c_int32(0)
+    keys = np.zeros(max(int(max_keys), 1), dtype=np.uint64)
+    with _on_device(ws.device):
+        _check(lib.stego_crf_lattice_info(byref(desc), _ptr(ws), ws.numel(), int(b), int(which), byref(n),
+                                          keys.ctypes.data if max_keys else None, int(max_keys), _stream()))
+    return n.value, keys[:min(n.value, int(max_keys))]

@@ -7,6 +7,7 @@
 #include "corr_common.h"
 #include "host_util.h"
 #include "../../include/stego_head.h"
+#include "../../include/stego_crf.h"
 #include "corr_wide.h"
 
 namespace stego {
@@ -355,6 +356,8 @@ const char* stego_error_string(int code)
         case STEGO_ERR_UNSUPPORTED: return "unsupported configuration (limits: S<=16, K<=128 (K>72: channels-last maps with C = 192 / 384 / 768, B <= compute units), n_neg<=254, fp32 maps, <2^31 elements per image, no unknown flags)";
         case STEGO_ERR_WORKSPACE: return "workspace too small";
         case STEGO_ERR_ALIGN: return "pointer not 4-byte aligned";
+        case STEGO_ERR_CRF_LIMITS: return "dense CRF limits: 1 <= C <= 64 labels, H * W * 6 < 2^31 (include/stego_crf.h)";
+        case STEGO_ERR_CRF_RANGE: return "dense CRF: a lattice coordinate would leave the packed key (image too large for its standard deviations)";
         default: return code >= STEGO_ERR_HIP ? "HIP runtime error (code - 1000 = hipError_t)" : "unknown error";
     }
 }

@@ -1,0 +1,117 @@
+"""The reference's evaluation loop (``src/eval_segmentation.py:118-161``) without figures, PiCIE or DataParallel: flip-averaged code,
+both probes, the dense CRF (stego_amd.crf, on the device) and the final metrics.
+
+    python -m stego_amd.eval_segmentation model_paths=[run.ckpt] run_crf=True       # a CroppedDataset val split, or synthetic data
+"""
+import sys
+from os.path import dirname, exists, join
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+from PIL import Image
+
+from .crf import batched_crf
+from .data import CroppedDataset, crop_dir
+from .train_segmentation import LitUnsupervisedSegmenter, SyntheticContrastiveDataset, load_config
+
+EVAL_CONFIG = join(dirname(__file__), "configs", "eval_config.yml")
+_MEAN = np.array([0.485, 0.456, 0.406], dtype=np.float32)
+_STD = np.array([0.229, 0.224, 0.225], dtype=np.float32)
+
+
+def _img_label(batch):
+    if isinstance(batch, dict):
+        return batch["img"], batch["label"]
+    return batch[0], batch[1]                    # CroppedDataset items: (image, target, mask)
+
+
+def evaluate(model, loader, run_crf=True, device=None):
+    """eval_segmentation.py:118-161 over `loader` (batches with "img" / "label", or (img, label, ...) tuples) -> the metrics dict of
+    model.test_linear_metrics and model.test_cluster_metrics (reset first, then updated batch by batch, then computed)."""
+    device = device or next(model.parameters()).device
+    model.eval()
+    model.test_linear_metrics.reset()
+    model.test_cluster_metrics.reset()
+    with torch.no_grad():
+        for batch in loader:
+            img, label = _img_label(batch)
+            img, label = img.to(device), label.to(device)
+            _, code1 = model.net(img)
+            _, code2 = model.net(img.flip(dims=[3]))
+            code = (code1 + code2.flip(dims=[3])) / 2
+            code = F.interpolate(code, label.shape[-2:], mode="bilinear", align_corners=False)
+            linear_probs = torch.log_softmax(model.linear_probe(code), dim=1)
+            cluster_probs = model.cluster_probe(code, 2, log_probs=True)
+            if run_crf:
+                linear_preds = batched_crf(None, img, linear_probs).argmax(1)
+                cluster_preds = batched_crf(None, img, cluster_probs).argmax(1)
+            else:
+                linear_preds = linear_probs.argmax(1)
+                cluster_preds = cluster_probs.argmax(1)
+            model.test_linear_metrics.update(linear_preds, label)
+            model.test_cluster_metrics.update(cluster_preds, label)
+    return {**model.test_linear_metrics.compute(), **model.test_cluster_metrics.compute()}
+
+
+def _resize_center_crop(im, res):
+    """The reference's get_transform(res, _, "center") on a PIL image (src/utils.py:164-183): torchvision Resize(res, Image.NEAREST)
+    for images and labels alike - the short side becomes res, the long side int(res * long / short) (truncated), and an image
+    whose short side already is res is left as it is - then CenterCrop(res) (offsets int(round((size - res) / 2)))."""
+    w, h = im.size
+    short, long = min(w, h), max(w, h)
+    if short != res:
+        new_long = int(res * long / short)
+        nw, nh = (res, new_long) if w <= h else (new_long, res)
+        im = im.resize((nw, nh), Image.NEAREST)
+    w, h = im.size
+    left, top = int(round((w - res) / 2.0)), int(round((h - res) / 2.0))
+    return im.crop((left, top, left + res, top + res))
+
+
+def image_transform(res):
+    """get_transform(res, False, "center"): resize + crop, ToTensor (x / 255), Normalize(ImageNet mean, std)."""
+    def f(im):
+        x = np.asarray(_resize_center_crop(im, res), dtype=np.float32) / np.float32(255.0)
+        return torch.from_numpy(((x - _MEAN) / _STD).transpose(2, 0, 1).copy())
+    return f
+
+
+def label_transform(res):
+    """get_transform(res, True, "center"): resize + crop, ToTargetTensor (int64 [1, res, res])."""
+    def f(im):
+        return torch.as_tensor(np.array(_resize_center_crop(im, res)), dtype=torch.int64).unsqueeze(0)
+    return f
+
+
+def make_loader(cfg, model):
+    """The val split of the cropped tree under cfg.pytorch_data_dir when it exists (crop_datasets.py's layout), else synthetic data."""
+    mcfg = model.cfg
+    root = getattr(cfg, "pytorch_data_dir", None)
+    crop_type, crop_ratio = getattr(mcfg, "crop_type", "five"), getattr(mcfg, "crop_ratio", 0.5)
+    if root and exists(join(crop_dir(root, mcfg.dataset_name, crop_type, crop_ratio), "img", "val")):
+        ds = CroppedDataset(root, mcfg.dataset_name, crop_type, crop_ratio, "val", transform=image_transform(cfg.res),
+                            target_transform=label_transform(cfg.res))
+    else:
+        print("no cropped val split under %r: synthetic data" % root)
+        ds = SyntheticContrastiveDataset(cfg.batch_size * 4, cfg.res, model.n_classes, seed=0)
+    return torch.utils.data.DataLoader(ds, cfg.batch_size * 2, shuffle=False, num_workers=getattr(cfg, "num_workers", 0))
+
+
+def my_app(cfg):
+    """eval_segmentation.py:57-161: every checkpoint of cfg.model_paths evaluated on the val split; returns {path: metrics}."""
+    results = {}
+    dev = torch.device("cuda", 0)
+    for model_path in cfg.model_paths:
+        model = LitUnsupervisedSegmenter.load_from_checkpoint(model_path)
+        model.eval().to(dev)
+        metrics = evaluate(model, make_loader(cfg, model), run_crf=cfg.run_crf, device=dev)
+        print("")
+        print(model_path)
+        print({k: float(v) for k, v in metrics.items()})
+        results[model_path] = metrics
+    return results
+
+
+if __name__ == "__main__":
+    my_app(load_config(EVAL_CONFIG, overrides=sys.argv[1:]))
