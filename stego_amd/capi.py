@@ -56,6 +56,22 @@ class StegoCrfDesc(Structure):
 CRF_ERR_LIMITS, CRF_ERR_RANGE = 20, 21
 
 
+class StegoDataItem(Structure):
+    """include/stego_data.h: one stored crop of the device image store"""
+    _fields_ = [("img_offset", c_int64), ("label_offset", c_int64)] + \
+        [(n, c_int32) for n in ("h", "w", "nh", "nw", "row_map", "col_map", "center_top", "center_left")]
+
+
+class StegoDataDesc(Structure):
+    """include/stego_data.h"""
+    _fields_ = [("N", c_int32), ("R", c_int32), ("n_items", c_int64), ("img_arena_bytes", c_int64), ("label_arena_bytes", c_int64),
+                ("map_pool_len", c_int64)]
+
+
+DATA_ERR_RES, DATA_ERR_COUNT, DATA_ERR_ITEM, DATA_ERR_RANGE, DATA_ERR_ORIGIN = 30, 31, 32, 33, 34
+DATA_MAX_RES, DATA_MAX_N = 2048, 65535
+
+
 _H = POINTER(StegoHeadDesc)
 _D = POINTER(StegoCorrDesc)
 _M = POINTER(StegoMap)
@@ -73,6 +89,8 @@ SIGNATURES = {
     "stego_crf_workspace_bytes": (c_size_t, [POINTER(StegoCrfDesc)]),
     "stego_crf_run": (c_int32, [POINTER(StegoCrfDesc), _P, _P, _P, _P, c_size_t, _P]),
     "stego_crf_lattice_info": (c_int32, [POINTER(StegoCrfDesc), _P, c_size_t, c_int32, c_int32, POINTER(c_int32), _P, c_int32, _P]),
+    "stego_data_check_items": (c_int32, [POINTER(StegoDataDesc), _P, POINTER(c_int64)]),
+    "stego_data_prepare": (c_int32, [POINTER(StegoDataDesc)] + [_P] * 10 + [_P]),
     "stego_abi_version": (c_int32, []),
     "stego_debug_set": (c_int32, [c_int32, c_int32]),
     "stego_debug_occupy": (c_int32, [c_int32, c_int32, c_int32, _P]),
@@ -908,3 +926,37 @@ def crf_lattice_info(desc, ws, b, which, max_keys=0):
         _check(lib.stego_crf_lattice_info(byref(desc), _ptr(ws), ws.numel(), int(b), int(which), byref(n),
                                           keys.ctypes.data if max_keys else None, int(max_keys), _stream()))
     return n.value, keys[:min(n.value, int(max_keys))]
+
+
+# ---- batch preparation of the device image store (include/stego_data.h; stego_amd.device_data builds the table and the arenas)
+def data_desc(N, R, n_items, img_arena_bytes, label_arena_bytes, map_pool_len):
+    return StegoDataDesc(int(N), int(R), int(n_items), int(img_arena_bytes), int(label_arena_bytes), int(map_pool_len))
+
+
+def data_check_items(desc, items_np):
+    """stego_data_check_items on a host numpy array of StegoDataItem records (host only) -> (rc, first bad record or -1)."""
+    bad = c_int64(-1)
+    rc = load().stego_data_check_items(byref(desc), items_np.ctypes.data, byref(bad))
+    return int(rc), int(bad.value)
+
+
+def data_prepare_raw(desc, items, img_arena, label_arena, map_pool, lut, index, origin, img, label, mask):
+    """stego_data_prepare with every buffer given (tests: the error codes) -> the return code, unchecked."""
+    with _on_device(img.device if img is not None else index.device):
+        return int(load().stego_data_prepare(byref(desc), _ptr(items), _ptr(img_arena), _ptr(label_arena), _ptr(map_pool), _ptr(lut),
+                                             _ptr(index), _ptr(origin), _ptr(img), _ptr(label), _ptr(mask), _stream()))
+
+
+def data_prepare(desc_args, items, img_arena, label_arena, map_pool, lut, index, origin=None):
+    """stego_data_prepare: index int64 [N] and origin int32 [N, 2] (or None: centre crops) on the device of the arenas ->
+    (img float32 [N,3,R,R], label int64 [N,R,R], mask bool [N,1,R,R]).  desc_args = (R, n_items, img bytes, label bytes, pool len)."""
+    _require_dev(items, img_arena, label_arena, map_pool, lut, index, origin)
+    R = int(desc_args[0])
+    N = int(index.numel())
+    dev = index.device
+    desc = data_desc(N, *desc_args)
+    img = torch.empty(N, 3, R, R, dtype=torch.float32, device=dev)
+    label = torch.empty(N, R, R, dtype=torch.int64, device=dev)
+    mask = torch.empty(N, 1, R, R, dtype=torch.bool, device=dev)
+    _check(data_prepare_raw(desc, items, img_arena, label_arena, map_pool, lut, index, origin, img, label, mask))
+    return img, label, mask

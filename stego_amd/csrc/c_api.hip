@@ -8,6 +8,7 @@
 #include "host_util.h"
 #include "../../include/stego_head.h"
 #include "../../include/stego_crf.h"
+#include "../../include/stego_data.h"
 #include "corr_wide.h"
 
 namespace stego {
@@ -357,6 +358,11 @@ const char* stego_error_string(int code)
         case STEGO_ERR_WORKSPACE: return "workspace too small";
         case STEGO_ERR_ALIGN: return "pointer not 4-byte aligned";
         case STEGO_ERR_CRF_LIMITS: return "dense CRF limits: 1 <= C <= 64 labels, H * W * 6 < 2^31 (include/stego_crf.h)";
+        case STEGO_ERR_DATA_RES: return "batch preparation: output side R outside [1, STEGO_DATA_MAX_RES] (include/stego_data.h)";
+        case STEGO_ERR_DATA_COUNT: return "batch preparation: N outside [1, STEGO_DATA_MAX_N] or n_items outside [1, 2^31)";
+        case STEGO_ERR_DATA_ITEM: return "batch preparation: a table record has h or w < 1, nh or nw < R, or a centre origin outside the resized image";
+        case STEGO_ERR_DATA_RANGE: return "batch preparation: a table record's bytes or index maps lie outside their arena / map pool";
+        case STEGO_ERR_DATA_ORIGIN: return "batch preparation: a crop origin outside the resized image";
         case STEGO_ERR_CRF_RANGE: return "dense CRF: a lattice coordinate would leave the packed key (image too large for its standard deviations)";
         default: return code >= STEGO_ERR_HIP ? "HIP runtime error (code - 1000 = hipError_t)" : "unknown error";
     }

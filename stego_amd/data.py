@@ -62,6 +62,81 @@ def write_cropped(root, dataset_name, crop_type, crop_ratio, split, items):
     return n
 
 
+_MEAN = np.array([0.485, 0.456, 0.406], dtype=np.float32)
+_STD = np.array([0.229, 0.224, 0.225], dtype=np.float32)
+
+
+def resized_size(w, h, res):
+    """(nw, nh) after torchvision Resize(res, NEAREST): the short side becomes res, the long side int(res * long / short) (truncated);
+    an image whose short side already is res keeps its size."""
+    short, long = min(w, h), max(w, h)
+    if short == res:
+        return w, h
+    new_long = int(res * long / short)
+    return (res, new_long) if w <= h else (new_long, res)
+
+
+def _resize(im, res):
+    nw, nh = resized_size(im.size[0], im.size[1], res)
+    return im if (nw, nh) == im.size else im.resize((nw, nh), Image.NEAREST)
+
+
+def _resize_center_crop(im, res):
+    """The reference's get_transform(res, _, "center") on a PIL image (src/utils.py:164-183): torchvision Resize(res, Image.NEAREST)
+    for images and labels alike - the short side becomes res, the long side int(res * long / short) (truncated), and an image
+    whose short side already is res is left as it is - then CenterCrop(res) (offsets int(round((size - res) / 2)))."""
+    im = _resize(im, res)
+    w, h = im.size
+    left, top = int(round((w - res) / 2.0)), int(round((h - res) / 2.0))
+    return im.crop((left, top, left + res, top + res))
+
+
+def random_crop_origin(h, w, res):
+    """torchvision RandomCrop.get_params on an h x w image: (0, 0) without a draw when it is res x res already, else
+    top = torch.randint(0, h - res + 1), left = torch.randint(0, w - res + 1) from torch's global generator."""
+    if h < res or w < res:
+        raise ValueError("Required crop size {} is larger than input image size {}".format((res, res), (h, w)))
+    if h == res and w == res:
+        return 0, 0
+    top = torch.randint(0, h - res + 1, size=(1,)).item()
+    left = torch.randint(0, w - res + 1, size=(1,)).item()
+    return top, left
+
+
+def _resize_random_crop(im, res):
+    """get_transform(res, _, "random"): Resize(res, NEAREST), then RandomCrop(res)."""
+    im = _resize(im, res)
+    top, left = random_crop_origin(im.size[1], im.size[0], res)
+    return im.crop((left, top, left + res, top + res))
+
+
+def _cropper(crop):
+    if crop == "center":
+        return _resize_center_crop
+    if crop == "random":
+        return _resize_random_crop
+    raise ValueError("Unknown Cropper {}".format(crop))
+
+
+def image_transform(res, crop="center"):
+    """get_transform(res, False, crop): resize + crop, ToTensor (x / 255), Normalize(ImageNet mean, std)."""
+    rc = _cropper(crop)
+
+    def f(im):
+        x = np.asarray(rc(im, res), dtype=np.float32) / np.float32(255.0)
+        return torch.from_numpy(((x - _MEAN) / _STD).transpose(2, 0, 1).copy())
+    return f
+
+
+def label_transform(res, crop="center"):
+    """get_transform(res, True, crop): resize + crop, ToTargetTensor (int64 [1, res, res])."""
+    rc = _cropper(crop)
+
+    def f(im):
+        return torch.as_tensor(np.array(rc(im, res)), dtype=torch.int64).unsqueeze(0)
+    return f
+
+
 def to_tensor(pil_img):
     """PIL RGB -> float [3,H,W] in [0,1] (torchvision's ToTensor)."""
     return torch.from_numpy(np.asarray(pil_img, dtype=np.uint8).copy()).permute(2, 0, 1).float().div(255)
@@ -107,3 +182,65 @@ class CroppedDataset(Dataset):
         with Image.open(join(self.label_dir, "%d.png" % index)) as lab:
             target = _seeded(self.target_transform, lab, seed) - 1      # the tree stores label + 1: 0 on disk = unlabelled
         return image, target.squeeze(0), target == -1
+
+
+class ContrastiveSegDataset(Dataset):
+    """The reference's training / evaluation dataset (src/data.py:419-565) for the cropped trees (cocostuff27, cityscapes with a
+    crop_type): CroppedDataset items at `transform` / `target_transform`, and with pos_images / pos_labels a KNN positive per item,
+    nns[ind][r] with r uniform in [1, num_neighbors] from the precomputed table {pytorch_data_dir}/nns/nns_{model_type}_{dataset}_
+    {image_set}_{crop_type}_{res}.npz.  The random draws come in the reference's order: the item's own CroppedDataset seed (numpy),
+    torch.randint for the neighbour rank, the positive's CroppedDataset seed, then one more numpy seed that reseeds python's and
+    torch's generators (what the reference's augmentations would draw from).  The img_aug / coord_aug augmentations are not built.
+
+    This is the CPU loader of train_segmentation when the split does not fit the device, and the oracle of
+    device_data.DeviceContrastiveLoader."""
+
+    def __init__(self, pytorch_data_dir, dataset_name, crop_type, image_set, transform, target_transform, cfg,
+                 aug_geometric_transform=None, aug_photometric_transform=None, num_neighbors=5, compute_knns=False, mask=False,
+                 pos_labels=False, pos_images=False, extra_transform=None, model_type_override=None):
+        super().__init__()
+        if crop_type is None or dataset_name not in ("cocostuff27", "cityscapes"):
+            raise ValueError("ContrastiveSegDataset reads the cropped trees only (cocostuff27 / cityscapes with a crop_type), "
+                             "got dataset %r, crop_type %r" % (dataset_name, crop_type))
+        if aug_geometric_transform is not None or aug_photometric_transform is not None:
+            raise ValueError("the img_aug / coord_aug augmentations are not supported")
+        self.num_neighbors, self.image_set, self.dataset_name = num_neighbors, image_set, dataset_name
+        self.mask, self.pos_labels, self.pos_images, self.extra_transform = mask, pos_labels, pos_images, extra_transform
+        self.n_classes = 27
+        self.dataset = CroppedDataset(pytorch_data_dir, dataset_name, crop_type, cfg.crop_ratio, image_set, transform=transform,
+                                      target_transform=target_transform)
+        model_type = model_type_override if model_type_override is not None else cfg.model_type
+        feature_cache_file = join(pytorch_data_dir, "nns", "nns_{}_{}_{}_{}_{}.npz".format(
+            model_type, dataset_name, image_set, crop_type, cfg.res))
+        self.feature_cache_file = feature_cache_file
+        if pos_labels or pos_images:
+            if not os.path.exists(feature_cache_file) or compute_knns:
+                raise ValueError("could not find nn file {} please run precompute_knns".format(feature_cache_file))
+            self.nns = np.load(feature_cache_file)["nns"]
+            assert len(self.dataset) == self.nns.shape[0]
+
+    def __len__(self):
+        return len(self.dataset)
+
+    def _set_seed(self, seed):
+        random.seed(seed)
+        torch.manual_seed(seed)
+
+    def __getitem__(self, ind):
+        pack = self.dataset[ind]
+        if self.pos_images or self.pos_labels:
+            ind_pos = self.nns[ind][torch.randint(low=1, high=self.num_neighbors + 1, size=[]).item()]
+            pack_pos = self.dataset[ind_pos]
+        seed = np.random.randint(2147483647)
+        self._set_seed(seed)
+        extra = self.extra_transform if self.extra_transform is not None else (lambda i, x: x)
+        ret = {"ind": ind, "img": extra(ind, pack[0]), "label": extra(ind, pack[1])}
+        if self.pos_images:
+            ret["img_pos"] = extra(ind, pack_pos[0])
+            ret["ind_pos"] = ind_pos
+        if self.mask:
+            ret["mask"] = pack[2]
+        if self.pos_labels:
+            ret["label_pos"] = extra(ind, pack_pos[1])
+            ret["mask_pos"] = pack_pos[2]
+        return ret

@@ -6,18 +6,14 @@ both probes, the dense CRF (stego_amd.crf, on the device) and the final metrics.
 import sys
 from os.path import dirname, exists, join
 
-import numpy as np
 import torch
 import torch.nn.functional as F
-from PIL import Image
 
 from .crf import batched_crf
-from .data import CroppedDataset, crop_dir
+from .data import _MEAN, _STD, CroppedDataset, _resize_center_crop, crop_dir, image_transform, label_transform  # noqa: F401
 from .train_segmentation import LitUnsupervisedSegmenter, SyntheticContrastiveDataset, load_config
 
 EVAL_CONFIG = join(dirname(__file__), "configs", "eval_config.yml")
-_MEAN = np.array([0.485, 0.456, 0.406], dtype=np.float32)
-_STD = np.array([0.229, 0.224, 0.225], dtype=np.float32)
 
 
 def _img_label(batch):
@@ -52,36 +48,6 @@ def evaluate(model, loader, run_crf=True, device=None):
             model.test_linear_metrics.update(linear_preds, label)
             model.test_cluster_metrics.update(cluster_preds, label)
     return {**model.test_linear_metrics.compute(), **model.test_cluster_metrics.compute()}
-
-
-def _resize_center_crop(im, res):
-    """The reference's get_transform(res, _, "center") on a PIL image (src/utils.py:164-183): torchvision Resize(res, Image.NEAREST)
-    for images and labels alike - the short side becomes res, the long side int(res * long / short) (truncated), and an image
-    whose short side already is res is left as it is - then CenterCrop(res) (offsets int(round((size - res) / 2)))."""
-    w, h = im.size
-    short, long = min(w, h), max(w, h)
-    if short != res:
-        new_long = int(res * long / short)
-        nw, nh = (res, new_long) if w <= h else (new_long, res)
-        im = im.resize((nw, nh), Image.NEAREST)
-    w, h = im.size
-    left, top = int(round((w - res) / 2.0)), int(round((h - res) / 2.0))
-    return im.crop((left, top, left + res, top + res))
-
-
-def image_transform(res):
-    """get_transform(res, False, "center"): resize + crop, ToTensor (x / 255), Normalize(ImageNet mean, std)."""
-    def f(im):
-        x = np.asarray(_resize_center_crop(im, res), dtype=np.float32) / np.float32(255.0)
-        return torch.from_numpy(((x - _MEAN) / _STD).transpose(2, 0, 1).copy())
-    return f
-
-
-def label_transform(res):
-    """get_transform(res, True, "center"): resize + crop, ToTargetTensor (int64 [1, res, res])."""
-    def f(im):
-        return torch.as_tensor(np.array(_resize_center_crop(im, res)), dtype=torch.int64).unsqueeze(0)
-    return f
 
 
 def make_loader(cfg, model):

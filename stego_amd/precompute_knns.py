@@ -6,9 +6,16 @@
   sharded_nearest_neighbors(local_feats, k)     SURVEY.md 8(e): rows sharded over the ranks of one node, one RCCL
                                                 all-gather of the feature matrix, every rank answers its own rows
   save_nns(path, nns)                           the reference's file format: np.savez_compressed(..., nns=...)
+  my_app(cfg)                                   reference :24-97 for the configured dataset and crop type:
+                                                    python -m stego_amd.precompute_knns pytorch_data_dir=/data
 
 The kernels live behind the C ABI (include/stego_corr.h: stego_knn_topk); there is no CPU path.
 """
+import os
+import random
+import sys
+from os.path import exists, join
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -91,3 +98,78 @@ def load_nns(path):
 def save_nns(path, nns):
     """Same on-disk format as the reference (:96): a compressed npz with the single key ``nns``."""
     np.savez_compressed(path, nns=nns.cpu().numpy() if torch.is_tensor(nns) else np.asarray(nns))
+
+
+KNN_RES = 224           # the reference hard-codes the resolution of the precompute (:45), and the file name carries it
+KNN_BATCH = 256         # :74
+
+
+def _feature_model(cfg):
+    """:49-58: the backbone's features, p[0] of DinoFeaturizer (dim does not matter), or the trunk without its last block."""
+    import torch.nn as nn
+    from .featurizers import DinoFeaturizer, LambdaLayer
+    if cfg.arch == "dino":
+        return nn.Sequential(DinoFeaturizer(20, cfg), LambdaLayer(lambda p: p[0]))
+    from .trunks import load_model
+    cut_model = load_model(cfg.model_type, join(cfg.output_root, "data"), allow_random_init=getattr(cfg, "allow_random_trunk", False))
+    return nn.Sequential(*list(cut_model.children())[:-1])
+
+
+def _split_loader(cfg, image_set, device):
+    """The split's centre crops at KNN_RES in order, from the device store; on the CPU (ContrastiveSegDataset) when it does not fit."""
+    from .data import ContrastiveSegDataset, image_transform, label_transform
+    from .device_data import DeviceContrastiveLoader, DeviceImageStore, StoreTooLarge
+    max_bytes = float(getattr(cfg, "device_dataset_max_gb", 200)) * 2 ** 30
+    try:
+        store = DeviceImageStore(cfg.pytorch_data_dir, cfg.dataset_name, cfg.crop_type, cfg.crop_ratio, image_set, device=device,
+                                 max_bytes=max_bytes)
+        return DeviceContrastiveLoader(store, None, batch_size=KNN_BATCH, res=KNN_RES, drop_last=False)
+    except StoreTooLarge as e:
+        print("%s: reading it on the CPU" % e)
+    ds = ContrastiveSegDataset(cfg.pytorch_data_dir, cfg.dataset_name, cfg.crop_type, image_set, image_transform(KNN_RES),
+                               label_transform(KNN_RES), cfg)
+    return torch.utils.data.DataLoader(ds, KNN_BATCH, shuffle=False, num_workers=getattr(cfg, "num_workers", 0))
+
+
+def my_app(cfg):
+    """precompute_knns.py:24-97 for cfg.dataset_name and cfg.crop_type: for the val and train splits of the cropped tree whose table
+    {pytorch_data_dir}/nns/nns_filename(...) does not exist yet, the mean-pooled, L2-normalised backbone features of the centre crops
+    at 224 and their 30 nearest neighbours, written with save_nns.  The backbone runs in eval mode (the reference leaves the
+    featurizer's feature dropout on).  Returns the paths written."""
+    from .data import crop_dir
+    pytorch_data_dir = cfg.pytorch_data_dir
+    os.makedirs(join(cfg.output_root, "data"), exist_ok=True)
+    os.makedirs(join(cfg.output_root, "logs"), exist_ok=True)
+    os.makedirs(join(pytorch_data_dir, "nns"), exist_ok=True)
+    random.seed(0)
+    np.random.seed(0)
+    torch.manual_seed(0)                      # seed_everything(0)
+    device = torch.device("cuda", torch.cuda.current_device())
+    model = None
+    written = []
+    for image_set in ["val", "train"]:
+        path = join(pytorch_data_dir, "nns", nns_filename(cfg.model_type, cfg.dataset_name, image_set, cfg.crop_type, KNN_RES))
+        if exists(path):
+            print("{} exists, skipping".format(path))
+            continue
+        if not exists(join(crop_dir(pytorch_data_dir, cfg.dataset_name, cfg.crop_type, cfg.crop_ratio), "img", image_set)):
+            print("no cropped {} split under {}: nothing to compute".format(image_set, pytorch_data_dir))
+            continue
+        print("{} not found, computing".format(path))
+        if model is None:
+            model = _feature_model(cfg).to(device).eval()
+        with torch.no_grad():
+            normed_feats = get_feats(model, _split_loader(cfg, image_set, device), device=device)
+            print(tuple(normed_feats.shape))
+            nearest_neighbors = compute_nearest_neighbors(normed_feats, k=30)
+        save_nns(path, nearest_neighbors)
+        print("Saved NNs", cfg.model_type, cfg.dataset_name, image_set)
+        written.append(path)
+    return written
+
+
+if __name__ == "__main__":
+    from .train_segmentation import load_config
+    from .utils import prep_args
+    prep_args()
+    my_app(load_config(overrides=sys.argv[1:]))

@@ -467,9 +467,86 @@ class Trainer:
         return metrics
 
 
+def checkpoint_path(cfg):
+    """Where my_app's Trainer writes the checkpoint of a run on real data (the reference's ModelCheckpoint dirpath,
+    {output_root}/checkpoints/{log_dir}/..., train_segmentation.py:393-396,482-486)."""
+    return join(cfg.output_root, "checkpoints", str(cfg.log_dir), "{}_{}.ckpt".format(cfg.dataset_name, cfg.experiment_name))
+
+
+def _real_loaders(cfg, trainer):
+    """train_segmentation.py:421-457 on the cropped tree: the training loader (the device store when cfg.device_dataset and the split
+    fits cfg.device_dataset_max_gb, else ContrastiveSegDataset on cfg.num_workers CPU workers) and the val loader (the cropped val
+    split at 320, centre crops; the reference's raw-COCO val reader is not part of this build)."""
+    import numpy as np
+    from .data import ContrastiveSegDataset, crop_dir, image_transform, label_transform
+    from .device_data import DeviceContrastiveLoader, DeviceImageStore, StoreTooLarge
+    from .precompute_knns import nns_filename
+    root = cfg.pytorch_data_dir
+    crop = getattr(cfg, "loader_crop_type", "center")
+    nns_path = join(root, "nns", nns_filename(cfg.model_type, cfg.dataset_name, "train", cfg.crop_type, cfg.res))
+    loader = None
+    if getattr(cfg, "device_dataset", True):
+        max_bytes = float(getattr(cfg, "device_dataset_max_gb", 200)) * 2 ** 30
+        try:
+            store = DeviceImageStore(root, cfg.dataset_name, cfg.crop_type, cfg.crop_ratio, "train", device=trainer.device,
+                                     max_bytes=max_bytes)
+        except StoreTooLarge as e:
+            print("training data: CPU loader (ContrastiveSegDataset, %d workers): %s (cfg.device_dataset_max_gb = %s)"
+                  % (cfg.num_workers, e, cfg.device_dataset_max_gb))
+        else:
+            if not os.path.exists(nns_path):
+                raise ValueError("could not find nn file {} please run precompute_knns".format(nns_path))
+            loader = DeviceContrastiveLoader(store, np.load(nns_path)["nns"], cfg.batch_size, cfg.num_neighbors, cfg.res, crop=crop,
+                                             seed=0, rank=trainer.rank, world=trainer.world, drop_last=True)
+            print("training data: device store (%d crops, %.2f GB on the device)" % (len(store), store.nbytes / 1e9))
+    else:
+        print("training data: CPU loader (ContrastiveSegDataset, %d workers): cfg.device_dataset is off" % cfg.num_workers)
+    if loader is None:
+        ds = ContrastiveSegDataset(root, cfg.dataset_name, cfg.crop_type, "train", image_transform(cfg.res, crop),
+                                   label_transform(cfg.res, crop), cfg, num_neighbors=cfg.num_neighbors, mask=True, pos_images=True,
+                                   pos_labels=True)
+        loader = torch.utils.data.DataLoader(ds, cfg.batch_size, shuffle=True, num_workers=cfg.num_workers, pin_memory=True,
+                                             drop_last=True)
+    val_loader = None
+    if os.path.exists(join(crop_dir(root, cfg.dataset_name, cfg.crop_type, cfg.crop_ratio), "img", "val")):
+        if getattr(cfg, "device_dataset", True):
+            try:
+                vstore = DeviceImageStore(root, cfg.dataset_name, cfg.crop_type, cfg.crop_ratio, "val", device=trainer.device,
+                                          max_bytes=float(getattr(cfg, "device_dataset_max_gb", 200)) * 2 ** 30)
+                val_loader = DeviceContrastiveLoader(vstore, None, cfg.batch_size, res=320, drop_last=False)
+            except StoreTooLarge as e:
+                print("val data: CPU loader: %s" % e)
+        if val_loader is None:
+            vds = ContrastiveSegDataset(root, cfg.dataset_name, cfg.crop_type, "val", image_transform(320), label_transform(320), cfg,
+                                        mask=True)
+            val_loader = torch.utils.data.DataLoader(vds, cfg.batch_size, shuffle=False, num_workers=cfg.num_workers, pin_memory=True)
+    else:
+        print("no cropped val split: training without validation")
+    return loader, val_loader
+
+
 def my_app(cfg):
+    """Trains on the cropped tree {pytorch_data_dir}/cropped/{dataset}_{crop_type}_crop_{ratio} when its train split exists (KNN
+    positives from precompute_knns' table), on synthetic data otherwise.  Returns the per-step losses."""
+    from .data import crop_dir
     torch.manual_seed(0)            # seed_everything(0), train_segmentation.py:403
     n_classes = get_class_labels(cfg.dataset_name)
+    root = getattr(cfg, "pytorch_data_dir", None)
+    if root and os.path.exists(join(crop_dir(root, cfg.dataset_name, cfg.crop_type, cfg.crop_ratio), "img", "train")):
+        if cfg.aug_alignment_weight > 0:
+            raise ValueError("cfg.aug_alignment_weight = %s: the img_aug / coord_aug augmentations need torchvision's photometric "
+                             "transforms, which this build does not have; set aug_alignment_weight=0 to train on real data"
+                             % cfg.aug_alignment_weight)
+        import random
+        import numpy as np
+        random.seed(0)
+        np.random.seed(0)
+        ckpt = checkpoint_path(cfg)
+        os.makedirs(dirname(ckpt), exist_ok=True)
+        trainer = Trainer(cfg.max_steps, log_every=cfg.scalar_log_freq, val_check_interval=cfg.val_freq, checkpoint_path=ckpt)
+        loader, trainer.val_loader = _real_loaders(cfg, trainer)
+        model = LitUnsupervisedSegmenter(n_classes, cfg)
+        return trainer.fit(model, loader)
     trainer = Trainer(cfg.max_steps)
     ds = SyntheticContrastiveDataset(max(cfg.batch_size * 8, 64), cfg.res, n_classes, seed=trainer.rank)
     loader = torch.utils.data.DataLoader(ds, cfg.batch_size, shuffle=True, num_workers=0, drop_last=True)
