@@ -72,6 +72,17 @@ DATA_ERR_RES, DATA_ERR_COUNT, DATA_ERR_ITEM, DATA_ERR_RANGE, DATA_ERR_ORIGIN = 3
 DATA_MAX_RES, DATA_MAX_N = 2048, 65535
 
 
+class StegoProbeDesc(Structure):
+    """include/stego_probe.h"""
+    _fields_ = [(n, c_int32) for n in ("B", "K", "h", "w", "H", "W", "n_lin", "n_clu", "lin_kind", "clu_kind")] + [("alpha", c_float)]
+
+
+PROBE_ERR_DIM, PROBE_ERR_SIZE, PROBE_ERR_OUTPUT = 40, 41, 42
+PROBE_SKIP, PROBE_LOG_PROBS, PROBE_PROBS, PROBE_ARGMAX = 0, 1, 2, 3
+PROBE_KINDS = {None: PROBE_SKIP, "log_probs": PROBE_LOG_PROBS, "probs": PROBE_PROBS, "argmax": PROBE_ARGMAX}
+PROBE_MAX_K, PROBE_MAX_N, PROBE_MAX_OUT = 128, 64, 2048
+
+
 _H = POINTER(StegoHeadDesc)
 _D = POINTER(StegoCorrDesc)
 _M = POINTER(StegoMap)
@@ -91,6 +102,8 @@ SIGNATURES = {
     "stego_crf_lattice_info": (c_int32, [POINTER(StegoCrfDesc), _P, c_size_t, c_int32, c_int32, POINTER(c_int32), _P, c_int32, _P]),
     "stego_data_check_items": (c_int32, [POINTER(StegoDataDesc), _P, POINTER(c_int64)]),
     "stego_data_prepare": (c_int32, [POINTER(StegoDataDesc)] + [_P] * 10 + [_P]),
+    "stego_probe_head": (c_int32, [POINTER(StegoProbeDesc), _M, _M] + [_P] * 5 + [_P]),
+    "stego_probe_head_plan": (c_size_t, [POINTER(StegoProbeDesc), POINTER(c_int32), POINTER(c_int32)]),
     "stego_abi_version": (c_int32, []),
     "stego_debug_set": (c_int32, [c_int32, c_int32]),
     "stego_debug_occupy": (c_int32, [c_int32, c_int32, c_int32, _P]),
@@ -960,3 +973,59 @@ def data_prepare(desc_args, items, img_arena, label_arena, map_pool, lut, index,
     mask = torch.empty(N, 1, R, R, dtype=torch.bool, device=dev)
     _check(data_prepare_raw(desc, items, img_arena, label_arena, map_pool, lut, index, origin, img, label, mask))
     return img, label, mask
+
+
+# ---- fused probe head (include/stego_probe.h; stego_amd.segment wraps it for a model)
+def probe_desc(B, K, h, w, H, W, n_lin, n_clu, lin_kind, clu_kind, alpha):
+    return StegoProbeDesc(int(B), int(K), int(h), int(w), int(H), int(W), int(n_lin), int(n_clu), int(lin_kind), int(clu_kind), float(alpha))
+
+
+def probe_head_plan(desc):
+    """stego_probe_head_plan (host only) -> (LDS bytes, tile rows, tile columns); 0 bytes for an invalid descriptor."""
+    ty, tx = c_int32(0), c_int32(0)
+    n = load().stego_probe_head_plan(byref(desc), byref(ty), byref(tx))
+    return int(n), ty.value, tx.value
+
+
+def probe_head_raw(desc, code, code_flip, lin_w, lin_b, centroids, lin_out, clu_out, stream=None):
+    """stego_probe_head with every argument given: `code` / `code_flip` are StegoMap (or None), the rest raw addresses or tensors
+    (tests: the error codes) -> the return code, unchecked."""
+    def addr(x):
+        return _ptr(x) if torch.is_tensor(x) else x
+    return int(load().stego_probe_head(byref(desc), byref(code) if code is not None else None,
+                                       byref(code_flip) if code_flip is not None else None, addr(lin_w), addr(lin_b), addr(centroids),
+                                       addr(lin_out), addr(clu_out), stream if stream is not None else None))
+
+
+def probe_head(code, code_flip, lin_w, lin_b, centroids, size, lin_kind, clu_kind, alpha):
+    """stego_probe_head: code (and code_flip, or None) float32 [B, K, h, w] with any strides, lin_w [n_lin, K], lin_b [n_lin],
+    centroids [n_clu, K] (L2-normalised) on one HIP device -> (linear output, cluster output), each None for a skipped probe,
+    float32 [B, n, H, W] for "log_probs" / "probs" and int64 [B, H, W] for "argmax"."""
+    _require_dev(code, code_flip, lin_w, lin_b, centroids)
+    B, K, h, w = code.shape
+    H, W = int(size[0]), int(size[1])
+    lk, ck = PROBE_KINDS[lin_kind], PROBE_KINDS[clu_kind]
+    n_lin = int(lin_w.shape[0]) if lk != PROBE_SKIP else 0
+    n_clu = int(centroids.shape[0]) if ck != PROBE_SKIP else 0
+    if code_flip is not None and tuple(code_flip.shape) != tuple(code.shape):
+        raise ValueError("code_flip %s does not match code %s" % (tuple(code_flip.shape), tuple(code.shape)))
+    dev = code.device
+
+    def out(kind, n):
+        if kind == PROBE_SKIP:
+            return None
+        if kind == PROBE_ARGMAX:
+            return torch.empty(B, H, W, dtype=torch.int64, device=dev)
+        return torch.empty(B, n, H, W, dtype=torch.float32, device=dev)
+
+    def weights(t, n):
+        return _dense(t, torch.float32) if t is not None and n else None
+    lw, lb, ce = weights(lin_w, n_lin), weights(lin_b, n_lin), weights(centroids, n_clu)
+    if lw is not None and tuple(lw.shape) != (n_lin, K) or ce is not None and tuple(ce.shape) != (n_clu, K):
+        raise ValueError("probe weights %s / %s do not match K = %d" % (None if lw is None else tuple(lw.shape),
+                                                                        None if ce is None else tuple(ce.shape), K))
+    lo, co = out(lk, n_lin), out(ck, n_clu)
+    desc = probe_desc(B, K, h, w, H, W, n_lin, n_clu, lk, ck, alpha)
+    with _on_device(dev):
+        _check(probe_head_raw(desc, _map(code), _map(code_flip) if code_flip is not None else None, lw, lb, ce, lo, co, _stream()))
+    return lo, co

@@ -9,6 +9,7 @@
 #include "../../include/stego_head.h"
 #include "../../include/stego_crf.h"
 #include "../../include/stego_data.h"
+#include "../../include/stego_probe.h"
 #include "corr_wide.h"
 
 namespace stego {
@@ -363,6 +364,9 @@ const char* stego_error_string(int code)
         case STEGO_ERR_DATA_ITEM: return "batch preparation: a table record has h or w < 1, nh or nw < R, or a centre origin outside the resized image";
         case STEGO_ERR_DATA_RANGE: return "batch preparation: a table record's bytes or index maps lie outside their arena / map pool";
         case STEGO_ERR_DATA_ORIGIN: return "batch preparation: a crop origin outside the resized image";
+        case STEGO_ERR_PROBE_DIM: return "probe head: K outside [1, 128] or an active probe's labels outside [1, 64] (include/stego_probe.h)";
+        case STEGO_ERR_PROBE_SIZE: return "probe head: B outside [1, 65535], code side outside [1, 65535] or output side outside [1, 2048]";
+        case STEGO_ERR_PROBE_OUTPUT: return "probe head: unknown output kind, or both probes skipped";
         case STEGO_ERR_CRF_RANGE: return "dense CRF: a lattice coordinate would leave the packed key (image too large for its standard deviations)";
         default: return code >= STEGO_ERR_HIP ? "HIP runtime error (code - 1000 = hipError_t)" : "unknown error";
     }

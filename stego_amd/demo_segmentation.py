@@ -1,0 +1,101 @@
+"""The reference's demo (``src/demo_segmentation.py``): a checkpoint run over a folder of the user's own images, one label map per
+image and probe written as a PNG.
+
+    python -m stego_amd.demo_segmentation model_path=run.ckpt image_dir=my_images experiment_name=mine
+
+Each batch goes through stego_amd.segment.segment: the backbone on the images and their mirror images, the fused probe head
+(csrc/probe_head.hip) and the dense CRF on the device.  Deviations from the reference: a prediction is named after the file's stem
+(os.path.splitext, the reference's name for every file with an extension), files PIL cannot open are skipped and named instead of
+ending the run, the files are read in sorted order, and DataParallel (`use_ddp`) is not supported.
+"""
+import os
+import sys
+from os.path import dirname, exists, isdir, join
+
+import numpy as np
+import torch
+from PIL import Image
+
+from .data import image_transform
+from .segment import segment
+from .train_segmentation import LitUnsupervisedSegmenter, load_config
+
+DEMO_CONFIG = join(dirname(__file__), "configs", "demo_config.yml")
+
+
+class UnlabeledImageFolder(torch.utils.data.Dataset):
+    """The files of `root` in sorted order; an item is (image tensor, file name), or (None, file name) for a file PIL cannot read."""
+
+    def __init__(self, root, transform):
+        super().__init__()
+        self.root = root
+        self.transform = transform
+        self.images = sorted(f for f in os.listdir(root) if not isdir(join(root, f)))
+
+    def __getitem__(self, index):
+        name = self.images[index]
+        try:
+            with Image.open(join(self.root, name)) as im:
+                image = im.convert("RGB")
+        except (OSError, ValueError, Image.DecompressionBombError):
+            return None, name
+        return self.transform(image), name
+
+    def __len__(self):
+        return len(self.images)
+
+
+def collate(items):
+    """-> (images [N, 3, res, res] or None, their names, the names of the unreadable files of the batch)."""
+    good = [(img, name) for img, name in items if img is not None]
+    bad = [name for img, name in items if img is None]
+    imgs = torch.stack([img for img, _ in good]) if good else None
+    return imgs, [name for _, name in good], bad
+
+
+def result_dir(cfg):
+    return join(cfg.output_root, "results", "predictions", cfg.experiment_name)
+
+
+def prediction_name(name):
+    """`photo.v2.jpg` -> `photo.v2.png` (the reference's ".".join(name.split(".")[:-1]) + ".png" for a name with an extension)."""
+    return os.path.splitext(name)[0] + ".png"
+
+
+def my_app(cfg):
+    """demo_segmentation.py:34-78: every readable image of cfg.image_dir -> {result_dir}/{linear,cluster}/{stem}.png (uint8 labels,
+    PIL mode "L").  Returns the written paths, linear and cluster interleaved in file order."""
+    if getattr(cfg, "use_ddp", False):
+        raise NotImplementedError("use_ddp: DataParallel is not supported by stego_amd.demo_segmentation (one device)")
+    if not exists(cfg.model_path):
+        raise FileNotFoundError("model_path %r does not exist" % cfg.model_path)
+    if not isdir(cfg.image_dir):
+        raise FileNotFoundError("image_dir %r is not a directory" % cfg.image_dir)
+    out = result_dir(cfg)
+    for sub in ("linear", "cluster"):
+        os.makedirs(join(out, sub), exist_ok=True)
+
+    dev = torch.device("cuda", 0)
+    model = LitUnsupervisedSegmenter.load_from_checkpoint(cfg.model_path)
+    model.eval().to(dev)
+    dataset = UnlabeledImageFolder(cfg.image_dir, image_transform(cfg.res, "center"))
+    loader = torch.utils.data.DataLoader(dataset, cfg.batch_size * 2, shuffle=False, num_workers=cfg.num_workers, collate_fn=collate)
+    written, skipped = [], []
+    for imgs, names, bad in loader:
+        skipped.extend(bad)
+        if imgs is None:
+            continue
+        linear, cluster = segment(model, imgs.to(dev), run_crf=getattr(cfg, "run_crf", True))
+        linear, cluster = linear.cpu().numpy(), cluster.cpu().numpy()
+        for j, name in enumerate(names):
+            for sub, pred in (("linear", linear[j]), ("cluster", cluster[j])):
+                path = join(out, sub, prediction_name(name))
+                Image.fromarray(pred.astype(np.uint8)).save(path)          # 2-D uint8: mode "L"
+                written.append(path)
+    if skipped:
+        print("skipped %d file(s) PIL cannot read: %s" % (len(skipped), ", ".join(skipped)))
+    return written
+
+
+if __name__ == "__main__":
+    my_app(load_config(DEMO_CONFIG, overrides=sys.argv[1:]))

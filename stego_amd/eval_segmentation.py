@@ -9,7 +9,7 @@ from os.path import dirname, exists, join
 import torch
 import torch.nn.functional as F
 
-from .crf import batched_crf
+from .crf import batched_crf, dense_crf_batch, image_to_bgr_u8
 from .data import _MEAN, _STD, CroppedDataset, _resize_center_crop, crop_dir, image_transform, label_transform  # noqa: F401
 from .train_segmentation import LitUnsupervisedSegmenter, SyntheticContrastiveDataset, load_config
 
@@ -22,9 +22,23 @@ def _img_label(batch):
     return batch[0], batch[1]                    # CroppedDataset items: (image, target, mask)
 
 
-def evaluate(model, loader, run_crf=True, device=None):
+def _fused_preds(model, img, code1, code2, size, run_crf):
+    """The same predictions from the fused probe head: the log-probabilities at the label's size `size`, or with run_crf the CRF's
+    probabilities straight from the kernel at the image's size, where the CRF runs (the unfused path resizes to it in _probs_at)."""
+    from .segment import probe_head
+    if not run_crf:
+        linear_probs, cluster_probs = probe_head(model, code1, code2, size, linear="log_probs", cluster="log_probs")
+        return linear_probs.argmax(1), cluster_probs.argmax(1)
+    linear_probs, cluster_probs = probe_head(model, code1, code2, img.shape[-2:], linear="probs", cluster="probs")
+    bgr = image_to_bgr_u8(img)
+    return dense_crf_batch(bgr, linear_probs).argmax(1), dense_crf_batch(bgr, cluster_probs).argmax(1)
+
+
+def evaluate(model, loader, run_crf=True, device=None, fused_head=False):
     """eval_segmentation.py:118-161 over `loader` (batches with "img" / "label", or (img, label, ...) tuples) -> the metrics dict of
-    model.test_linear_metrics and model.test_cluster_metrics (reset first, then updated batch by batch, then computed)."""
+    model.test_linear_metrics and model.test_cluster_metrics (reset first, then updated batch by batch, then computed).
+    fused_head: the flip average, resize and both probes in one launch (stego_amd.segment.probe_head), which writes the CRF's
+    probabilities directly (run_crf) or the log-probabilities the argmax takes, instead of the torch chain."""
     device = device or next(model.parameters()).device
     model.eval()
     model.test_linear_metrics.reset()
@@ -35,16 +49,19 @@ def evaluate(model, loader, run_crf=True, device=None):
             img, label = img.to(device), label.to(device)
             _, code1 = model.net(img)
             _, code2 = model.net(img.flip(dims=[3]))
-            code = (code1 + code2.flip(dims=[3])) / 2
-            code = F.interpolate(code, label.shape[-2:], mode="bilinear", align_corners=False)
-            linear_probs = torch.log_softmax(model.linear_probe(code), dim=1)
-            cluster_probs = model.cluster_probe(code, 2, log_probs=True)
-            if run_crf:
-                linear_preds = batched_crf(None, img, linear_probs).argmax(1)
-                cluster_preds = batched_crf(None, img, cluster_probs).argmax(1)
+            if fused_head:
+                linear_preds, cluster_preds = _fused_preds(model, img, code1, code2, label.shape[-2:], run_crf)
             else:
-                linear_preds = linear_probs.argmax(1)
-                cluster_preds = cluster_probs.argmax(1)
+                code = (code1 + code2.flip(dims=[3])) / 2
+                code = F.interpolate(code, label.shape[-2:], mode="bilinear", align_corners=False)
+                linear_probs = torch.log_softmax(model.linear_probe(code), dim=1)
+                cluster_probs = model.cluster_probe(code, 2, log_probs=True)
+                if run_crf:
+                    linear_preds = batched_crf(None, img, linear_probs).argmax(1)
+                    cluster_preds = batched_crf(None, img, cluster_probs).argmax(1)
+                else:
+                    linear_preds = linear_probs.argmax(1)
+                    cluster_preds = cluster_probs.argmax(1)
             model.test_linear_metrics.update(linear_preds, label)
             model.test_cluster_metrics.update(cluster_preds, label)
     return {**model.test_linear_metrics.compute(), **model.test_cluster_metrics.compute()}
@@ -71,7 +88,7 @@ def my_app(cfg):
     for model_path in cfg.model_paths:
         model = LitUnsupervisedSegmenter.load_from_checkpoint(model_path)
         model.eval().to(dev)
-        metrics = evaluate(model, make_loader(cfg, model), run_crf=cfg.run_crf, device=dev)
+        metrics = evaluate(model, make_loader(cfg, model), run_crf=cfg.run_crf, device=dev, fused_head=getattr(cfg, "fused_head", False))
         print("")
         print(model_path)
         print({k: float(v) for k, v in metrics.items()})
