@@ -490,7 +490,9 @@ struct HeadWgradParams {
     const float* maskX;        // X'[t][c] = X[t][c] * maskX[b * mask_ld + c]: [B, Kc] (mask_ld = Kc) or one row of ones (mask_ld = 0); never null
     int mask_ld;
     float* part;               // [splits][N][Kc] partial sums
-    float* part_bias;          // [splits][N] partial column sums of G (written by channel tile 0) or null
+    double* part_bias;         // [splits][N] partial column sums of G (written by channel tile 0) or null.  The bias gradients are
+                               // these sums, carried in fp64 from the first addition to the last (in fp32 - per thread, per token-row
+                               // group, then split after split - a 1-element db came out 3.7x less accurate than torch's pairwise sum)
     const unsigned* amax_g;    // largest |G| / |X| (see head_scale) or null
     const unsigned* amax_x;
     int M, N, Kc, splits;
@@ -546,7 +548,7 @@ __global__ void __launch_bounds__(256) head_wgrad_tr_kernel(const HeadWgradParam
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    f32x4 bsum = f32x4{0.f, 0.f, 0.f, 0.f};
+    double bsum[4] = {0.0, 0.0, 0.0, 0.0};
     const float sg = head_scale(prm.amax_g), sx = head_scale(prm.amax_x);
     const float unscale = 1.f / (sg * sx);
     const int Bimg = (prm.M + prm.HW - 1) / prm.HW;
@@ -604,7 +606,7 @@ __global__ void __launch_bounds__(256) head_wgrad_tr_kernel(const HeadWgradParam
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float gq = rg[q][e] * (okf * nkeep[e]);
-                bsum[e] += gq;
+                bsum[e] += (double)gq;
                 vg[e] = gq * sg;
                 vx[e] = rx[q][e] * (mk[e] * (sx * okf * ckeep[e]));
             }
@@ -671,16 +673,18 @@ __global__ void __launch_bounds__(256) head_wgrad_tr_kernel(const HeadWgradParam
             }
     }
     if (blockIdx.y == 0 && prm.part_bias) {       // column sums of G': 8 partial rows (one per token-row group) through the dead stages
-        f32x4* cs = reinterpret_cast<f32x4*>(lds);
-        cs[trow * 32 + c4] = bsum;
+        double* cs = reinterpret_cast<double*>(lds);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) cs[(trow * 32 + c4) * 4 + e] = bsum[e];
         __syncthreads();
         if (tid < 32) {
-            f32x4 t = cs[tid];
 #pragma unroll
-            for (int r = 1; r < 8; ++r) t += cs[r * 32 + tid];
+            for (int e = 0; e < 4; ++e) {
+                double t = cs[tid * 4 + e];
 #pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (n0 + 4 * tid + e < prm.N) prm.part_bias[(size_t)split * prm.N + n0 + 4 * tid + e] = t[e];
+                for (int r = 1; r < 8; ++r) t += cs[(r * 32 + tid) * 4 + e];
+                if (n0 + 4 * tid + e < prm.N) prm.part_bias[(size_t)split * prm.N + n0 + 4 * tid + e] = t;
+            }
         }
     }
 }
@@ -691,7 +695,7 @@ __global__ void __launch_bounds__(256) head_wgrad_tr_kernel(const HeadWgradParam
 __global__ void __launch_bounds__(256) head_wgrad_kernel(const HeadWgradParams prm)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];      // two stages of [G 16 KB][X 16 KB] (double buffer)
-    __shared__ float colsum[2][HT];
+    __shared__ double colsum[2][HT];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
     const int n0 = blockIdx.x * HT, c0 = blockIdx.y * HT, split = blockIdx.z;
     // token range of this split: whole stages of 32 tokens
@@ -708,7 +712,7 @@ __global__ void __launch_bounds__(256) head_wgrad_kernel(const HeadWgradParams p
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    float bsum = 0.f;
+    double bsum = 0.0;
     const float sg = head_scale(prm.amax_g), sx = head_scale(prm.amax_x);
     const float unscale = 1.f / (sg * sx);
 
@@ -747,7 +751,7 @@ __global__ void __launch_bounds__(256) head_wgrad_kernel(const HeadWgradParams p
             // (zeroing by a 0 / 1 factor, not by a select: a value that is only used conditionally has its load sunk into a branch)
             const float okf = m < prm.M ? 1.f : 0.f;
             const float gq = rg[e] * (okf * n_keep);
-            if (blockIdx.y == 0) bsum += gq;
+            if (blockIdx.y == 0) bsum += (double)gq;
             vg[e] = gq * sg;
             vx[e] = rx[e] * ((mcl >= first1 ? rk1 : rk0) * (sx * okf * c_keep));
         }
@@ -801,7 +805,7 @@ __global__ void __launch_bounds__(256) head_wgrad_kernel(const HeadWgradParams p
 // fourth partial tile each (loads of 16 tiles in flight per lane), then wave 0 adds the four wave sums in wave order: the order of the
 // additions is fixed, the result bitwise repeatable.  (One thread per run summing all tiles alone: 144 workgroups, 50 MB in 52 us.)
 __global__ void __launch_bounds__(256) head_reduce_kernel(const float* part, int splits, long long numel, float* dW,
-                                                          const float* part_bias, int N, float* db, float* db_b)
+                                                          const double* part_bias, int N, float* db, float* db_b)
 {
     __shared__ f32x4 wsum[4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -823,10 +827,10 @@ __global__ void __launch_bounds__(256) head_reduce_kernel(const float* part, int
     if (wave == 0 && ok) *reinterpret_cast<f32x4*>(dW + i) = ((wsum[0][lane] + wsum[1][lane]) + wsum[2][lane]) + wsum[3][lane];
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (part_bias && t < N) {
-        float sb = 0.f;
+        double sb = 0.0;
         for (int kk = 0; kk < splits; ++kk) sb += part_bias[(size_t)kk * N + t];
-        if (db) db[t] = sb;
-        if (db_b) db_b[t] = sb;
+        if (db) db[t] = (float)sb;
+        if (db_b) db_b[t] = (float)sb;
     }
 }
 
@@ -980,11 +984,11 @@ size_t stego_head_bwd_workspace_bytes(const StegoHeadDesc* d)
     if (head_check(d) != STEGO_OK) return 0;
     const size_t M = (size_t)d->B * d->HW;
     size_t part = (size_t)wgrad_splits(d, d->K) * d->K * d->C, pbias = (size_t)wgrad_splits(d, d->K) * d->K;
-    size_t total = 256 + round256((size_t)d->C * 4) + round256(part * 4) + round256(pbias * 4);
+    size_t total = 256 + round256((size_t)d->C * 4) + round256(part * 4) + round256(pbias * 8);
     if (d->nonlinear) {
         total += planes_bytes(d->C, d->K, wide_blocks(d->C));                              // W22^T planes
         total += round256(M * d->C * 4);                                                   // dHpre
-        total += round256((size_t)wgrad_splits(d, d->C) * d->C * d->C * 4) + round256((size_t)wgrad_splits(d, d->C) * d->C * 4);
+        total += round256((size_t)wgrad_splits(d, d->C) * d->C * d->C * 4) + round256((size_t)wgrad_splits(d, d->C) * d->C * 8);
     }
     return total + 256;
 }
@@ -1103,10 +1107,10 @@ int stego_head_bwd(const StegoHeadDesc* d, const float* tokens, const float* mas
         if ((e0 = absmax(d_code, (long long)d->HW * K, K, d->HW, M, K, HS_G)) != hipSuccess) return STEGO_ERR_HIP + (int)e0;
     }
     float* part_k = reinterpret_cast<float*>(ws); ws += round256((size_t)sk * K * C * 4);
-    float* pbias_k = reinterpret_cast<float*>(ws); ws += round256((size_t)sk * K * 4);
+    double* pbias_k = reinterpret_cast<double*>(ws); ws += round256((size_t)sk * K * 8);
     hipError_t e;
     auto wgrad = [&](const float* G, int ldg, int N, const float* X, long long x_img, long long x_tok, const float* maskX,
-                     float* part, float* pbias, int splits, float* dW, float* db, float* db_b) -> hipError_t {
+                     float* part, double* pbias, int splits, float* dW, float* db, float* db_b) -> hipError_t {
         HeadWgradParams w{};
         w.G = G; w.ldg = ldg; w.X = X; w.x_img = x_img; w.x_tok = x_tok; w.HW = d->HW;
         w.maskX = maskX ? maskX : ones; w.mask_ld = maskX ? C : 0;
@@ -1141,10 +1145,10 @@ int stego_head_bwd(const StegoHeadDesc* d, const float* tokens, const float* mas
     // dHpre = (G W22) * 1[H > 0]
     float* dH = reinterpret_cast<float*>(ws); ws += round256((size_t)M * C * 4);
     float* part_c = reinterpret_cast<float*>(ws); ws += round256((size_t)sc * C * C * 4);
-    float* pbias_c = reinterpret_cast<float*>(ws);
+    double* pbias_c = reinterpret_cast<double*>(ws);
     const int nwb = wide_blocks(C);
     HeadPrepParams prep{};
-    unsigned char* wsp = reinterpret_cast<unsigned char*>(pbias_c) + round256((size_t)sc * C * 4);
+    unsigned char* wsp = reinterpret_cast<unsigned char*>(pbias_c) + round256((size_t)sc * C * 8);
     const HeadPlanes pwt = carve_planes(wsp, prep.job[0], w22, C, K, C, 1, nwb, scl + HS_W22);      // B[n = channel j][k] = w22[k][j]
     // (W22's scale word holds the forward's maximum of the same matrix: raising it to the same value again is a no-op, no zeroing)
     hipLaunchKernelGGL(head_prep_absmax_kernel, dim3(1, PREP_WG), dim3(256), 0, s, prep);

@@ -84,7 +84,8 @@ def _compare(q, ref, atol, min_agree=1.0):
     return err, agree
 
 
-@pytest.mark.parametrize("H,W,C", [(1, 1, 3), (7, 13, 1), (7, 13, 27), (37, 53, 3), (37, 53, 27), (37, 53, 64), (16, 24, 64)])
+@pytest.mark.parametrize("H,W,C", [(1, 1, 3), (7, 13, 1), (7, 13, 27), (37, 53, 3), (37, 53, 27), (37, 53, 64), (16, 24, 64),
+                                   (7, 13, 6), (37, 53, 12)])     # (iterate<G>: G = 1, 8, 16 above; G = 2 for 5 <= C <= 8, G = 4 for 9..16)
 def test_small_shapes_match_oracle(H, W, C):
     bgr, probs = _case("noise", 2, C, H, W, seed=H * 1000 + W + C)
     q, ws, desc = _gpu(bgr, probs, keep=True)

@@ -133,3 +133,71 @@ def test_tensor_correlation_gradients_run_on_the_native_kernel(shape):
     for got, want in ((out, ref), (a1.grad, a2.grad), (b1.grad, b2.grad)):
         err = (got.double() - want).abs().max() / want.abs().max()
         assert float(err) < 2e-6, float(err)
+
+
+def _cl_map(x):
+    """A channels-last HIP copy of the NCHW numpy map, as a [B, C, H, W] view."""
+    return torch.from_numpy(x).to(DEV).permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+
+
+def _varied(rng, B, C, H, W):
+    return (rng.standard_normal((B, C, H, W)) * rng.uniform(0.2, 5.0, (B, 1, H, W))).astype(np.float32)      # pixel norms vary
+
+
+def _fp32_class_err(out, ref):
+    return float(np.abs(out - ref).max() / max(np.abs(ref).max(), 1e-30))
+
+
+# dense_rowblock_kernel<false> (A consumed in place, B prepared): launch_dense_corr takes it for channels-last maps with C % 8 == 0 and
+# NCH <= 6 that the stream kernel does not take, i.e. C <= 64 (here) or B rows not dense (the cropped view below)
+@pytest.mark.parametrize("normalize", [True, False])
+@pytest.mark.parametrize("C", [8, 32, 64])
+def test_dense_rowblock_kernel_narrow_channels(C, normalize):
+    """C in {8, 32, 64} (one partial / one whole 64-channel chunk); 117 x 77 pixels: a partial row block and a partial column block."""
+    from stego_amd import capi
+    B, H1, W1, H2, W2 = 2, 9, 13, 7, 11
+    rng = np.random.default_rng(C + 11 * normalize)
+    a, b = _varied(rng, B, C, H1, W1), _varied(rng, B, C, H2, W2)
+    out = capi.dense_corr(_cl_map(a), _cl_map(b), normalize=normalize).cpu().numpy()
+    ref = _ref(a, b, normalize)
+    np.testing.assert_allclose(out, ref, rtol=1e-3, atol=2e-5 * max(np.abs(ref).mean(), 1e-3) + 1e-6)
+    assert _fp32_class_err(out, ref) < 2e-6                            # the fp32-class bar of test_dense_stream_kernel_shapes
+
+
+# dense_rowblock_kernel<false> through the cropped-view condition: C = 384 (the stream kernel's width) but b.sh != W2 * b.sw
+@pytest.mark.parametrize("normalize", [True, False])
+def test_dense_rowblock_kernel_cropped_b_view(normalize):
+    from stego_amd import capi
+    B, C = 2, 384
+    rng = np.random.default_rng(21 + normalize)
+    a, b = _varied(rng, B, C, 14, 14), _varied(rng, B, C, 16, 17)
+    tb = _cl_map(b)[:, :, 1:-1, 2:-1]
+    assert tb.stride(2) != tb.shape[3] * tb.stride(3) and tb.stride(1) == 1
+    out = capi.dense_corr(_cl_map(a), tb, normalize=normalize).cpu().numpy()
+    ref = _ref(a, b[:, :, 1:-1, 2:-1], normalize)
+    np.testing.assert_allclose(out, ref, rtol=1e-3, atol=2e-5 * max(np.abs(ref).mean(), 1e-3) + 1e-6)
+    assert _fp32_class_err(out, ref) < 2e-6
+
+
+# one input through all three channels-last kernels: dense_stream (default), dense_rowblock_kernel<false> (STEGO_DEBUG bit 21) and
+# dense_prep_kernel + dense_tile_kernel (STEGO_DEBUG 8192)
+@pytest.mark.parametrize("normalize", [True, False])
+@pytest.mark.parametrize("C", [136, 384])
+def test_dense_corr_every_kernel_on_one_input(C, normalize):
+    from stego_amd import capi
+    base = int(os.environ.get("STEGO_DEBUG", "0"))
+    B, H1, W1, H2, W2 = 3, 9, 13, 12, 12
+    rng = np.random.default_rng(C + normalize)
+    a, b = _varied(rng, B, C, H1, W1), _varied(rng, B, C, H2, W2)
+    ta, tb = _cl_map(a), _cl_map(b)
+    ref = _ref(a, b, normalize)
+    outs = {}
+    try:
+        for name, bits in (("stream", 0), ("rowblock", 1 << 21), ("tile", 8192)):
+            capi.debug_set("STEGO_DEBUG", (base & ~((1 << 21) | 8192)) | bits)
+            outs[name] = capi.dense_corr(ta, tb, normalize=normalize).cpu().numpy()
+    finally:
+        capi.debug_set("STEGO_DEBUG", base)
+    for name, out in outs.items():
+        np.testing.assert_allclose(out, ref, rtol=1e-3, atol=2e-5 * max(np.abs(ref).mean(), 1e-3) + 1e-6, err_msg=name)
+        assert _fp32_class_err(out, ref) < 2e-6, (name, _fp32_class_err(out, ref))

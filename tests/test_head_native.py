@@ -44,8 +44,21 @@ def _reference_head_fp64(net, image_feat, masks):
     return x * m3, code, ambiguous
 
 
+_ARCH_C = {"vit_tiny": 192, "vit_small": 384, "vit_base": 768}
+# head_gemm_kernel<true, EPI_BIAS_RELU, 1> (forward H) and <false, EPI_MASK_POS, 1> (backward dHpre): wide_blocks(C) == 1, C % 384 != 0
+_NARROW_C = [("vit_tiny", 4, (28, 28), 70, "nonlinear")]
+# head_wgrad_kernel (the non-transposing weight gradient): stego_head_bwd's wgrad takes it when HW < 32; and the forward's mask slots:
+# n_slot = min(B, 127 / HW + 2) images per 128-row tile (9 at HW = 16, 7 at HW = 25, 6 at HW = 31), B large enough to fill them
+_SHORT_MAPS = [(arch, B, hw, 70, "nonlinear") for arch in _ARCH_C for B, hw in ((24, (4, 4)), (16, (5, 5)), (12, (1, 31)))]
+# code widths K (the N of the cluster1 / cluster2[2] GEMMs and of the dW1 / dW22 tiles) from one column to a full 128-column tile
+_CODE_WIDTHS = [("vit_small", 2, (14, 14), K, proj) for K in (1, 27, 64, 128) for proj in ("linear", "nonlinear")]
+# M = B * HW below one 128-row tile and not a multiple of it; the production batch 2B = 64 at 28 x 28
+_ROW_COUNTS = [("vit_small", 3, (3, 11), 70, "nonlinear"), ("vit_small", 64, (28, 28), 70, "nonlinear")]
+
+
 @pytest.mark.parametrize("arch,B,hw,dim,proj", [("vit_small", 4, (14, 14), 70, "nonlinear"), ("vit_small", 3, (9, 13), 70, "linear"),
-                                                 ("vit_base", 2, (10, 10), 100, "nonlinear"), ("vit_small", 32, (28, 28), 70, "nonlinear")])
+                                                 ("vit_base", 2, (10, 10), 100, "nonlinear"), ("vit_small", 32, (28, 28), 70, "nonlinear")]
+                         + _NARROW_C + _SHORT_MAPS + _CODE_WIDTHS + _ROW_COUNTS)
 def test_native_head_matches_the_reference_head_with_the_same_dropout_draws(arch, B, hw, dim, proj):
     net, cfg = _featurizer(arch, dim, proj, True)
     net.train()
@@ -79,6 +92,9 @@ def test_native_head_matches_the_reference_head_with_the_same_dropout_draws(arch
     masks = [net._feature_noise(image_feat).view(B, C) for _ in range(3 if proj == "nonlinear" else 1)]
     if proj != "nonlinear":
         masks = [masks[0], masks[0], net._feature_noise(image_feat).view(B, C)]
+    if B > 1:                                          # distinct masks per image: a mask row taken from the wrong image shows
+        for m in masks:
+            assert len({tuple(r) for r in m.cpu().tolist()}) == B
     x64 = image_feat.double().requires_grad_(False)
     for p in params:
         p.grad = None
@@ -88,6 +104,10 @@ def test_native_head_matches_the_reference_head_with_the_same_dropout_draws(arch
     err_n = float((c_n.double() - c64).abs().max())
     err_t = float((c_t.double() - c64).abs().max())
     assert err_n <= 2.0 * err_t + 1e-6, (err_n, err_t)           # the split-fp16 head is in the fp32 class of the torch head
+    for b in range(B):                                           # ... image by image (each has its own mask rows)
+        eb_n = float((c_n[b].double() - c64[b]).abs().max())
+        eb_t = float((c_t[b].double() - c64[b]).abs().max())
+        assert eb_n <= 2.0 * eb_t + 1e-6, (b, eb_n, eb_t)
     for (name, p), gn, gt, g64 in zip([(n, p) for n, p in net.named_parameters() if n.startswith("cluster")], g_n, g_t, net64_grads):
         if name.startswith("cluster2.0.") and ambiguous is not None and bool(ambiguous.any()):
             keep = ~ambiguous                     # rows of dW21 / entries of db21 whose relu' is well defined
@@ -217,3 +237,71 @@ def test_cpp_head_function_is_the_python_one_bit_for_bit():
         res[native_autograd] = rec
     for a, b in zip(res[True], res[False]):
         assert torch.equal(a, b)
+
+
+def _head_torch(tokens, masks, P, up, dtype):
+    """modules.py:108-112 on the token matrix in `dtype`, with explicit channel masks: code, the six parameter gradients of
+    sum(code * up), and cluster2[0]'s pre-activation."""
+    x = tokens.to(dtype)
+    m1, m2 = [m.to(dtype)[:, None, :] for m in masks[:2]]
+    ps = [P[n].detach().to(dtype).requires_grad_(True) for n in ("w1", "b1", "w21", "b21", "w22", "b22")]
+    w1, b1, w21, b21, w22, b22 = ps
+    pre = (x * m2) @ w21.T + b21
+    code = (x * m1) @ w1.T + b1 + torch.relu(pre) @ w22.T + b22
+    return code.detach(), torch.autograd.grad((code * up.to(dtype)).sum(), ps), pre.detach()
+
+
+def _head_params(C, K, seed, b21_shift=0.0):
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    u = lambda *shape: (torch.rand(*shape, device=DEV, generator=g) * 2 - 1) / C ** 0.5       # Conv2d's default init range
+    return dict(w1=u(K, C), b1=u(K), w21=u(C, C), b21=u(C) + b21_shift, w22=u(K, C), b22=u(K))
+
+
+# operand-scale edges of head_scale (the power-of-two prescale taken from each operand's largest magnitude), through the C ABI:
+# tokens x 1e-3 / x 1e3, all-zero tokens (scale word 0), a ReLU-dead hidden layer (H = 0, its scale word 0), one image masked out;
+# at C = 384, HW = 49 (head_gemm_kernel<.., 3>, head_wgrad_tr_kernel) and C = 192, HW = 16 (NW = 1 GEMMs, head_wgrad_kernel, 9 slots)
+@pytest.mark.parametrize("B,HW,C", [(6, 49, 384), (20, 16, 192)])
+@pytest.mark.parametrize("edge", ["tokens_x1e-3", "tokens_x1e3", "zero_tokens", "relu_dead", "zero_mask_image"])
+def test_native_head_operand_scale_edges_against_fp64(edge, B, HW, C):
+    K = 70
+    g = torch.Generator(device=DEV).manual_seed(HW + C)
+    full = torch.randn(B, 1 + HW, C, device=DEV, generator=g)
+    scale = {"tokens_x1e-3": 1e-3, "tokens_x1e3": 1e3, "zero_tokens": 0.0}.get(edge, 1.0)
+    full *= scale
+    tokens = full[:, 1:, :]                                            # the backbone's layout: the class token skipped by the view
+    masks = [((torch.rand(B, C, device=DEV, generator=g) < 0.9).float() / 0.9).contiguous() for _ in range(3)]
+    if edge == "zero_mask_image":
+        for m in masks:
+            m[1] = 0.0
+    P = _head_params(C, K, seed=C, b21_shift=-1e3 if edge == "relu_dead" else 0.0)
+    up = torch.randn(B, HW, K, device=DEV, generator=g) / HW
+    code, feats, saved_h = capi.head_fwd(tokens, masks, P["w1"], P["b1"], P["w21"], P["b21"], P["w22"], P["b22"], True, True)
+    grads = capi.head_bwd(tokens, masks, saved_h, P["w22"], up, K)
+    torch.cuda.synchronize()
+    c64, g64, pre64 = _head_torch(tokens, masks, P, up, torch.float64)
+    c32, g32, _ = _head_torch(tokens, masks, P, up, torch.float32)
+    if edge == "relu_dead":
+        assert bool((pre64 < 0).all())
+    assert torch.equal(feats, tokens * masks[2][:, None, :])           # the returned dropout(image_feat): the same fp32 product
+    outs = [("code", code, c32, c64)] + [("grad %s" % n, a, t, r) for n, a, t, r in zip(("w1", "b1", "w21", "b21", "w22", "b22"),
+                                                                                         grads, g32, g64)]
+    ambiguous = (pre64.abs() < 1e-5 * max(1.0, float(pre64.abs().max()))).flatten(0, 1).any(0)       # relu' undefined at fp32 accuracy
+    for name, got, t32, r64 in outs:
+        assert bool(torch.isfinite(got).all()), name
+        assert bool((got[r64 == 0] == 0).all()), (name, "not exactly zero where fp64 is")
+        if name in ("grad w21", "grad b21") and bool(ambiguous.any()):
+            keep = ~ambiguous
+            assert int(keep.sum()) >= 0.5 * keep.numel()
+            got, t32, r64 = got[keep], t32[keep], r64[keep]
+        if name == "code":
+            assert_close(got.cpu().numpy(), r64.cpu().numpy(), rtol=1e-3, atol_frac=1e-4, what=name)
+            for b in range(B):
+                en, et = float((got[b].double() - r64[b]).abs().max()), float((t32[b].double() - r64[b]).abs().max())
+                assert en <= 2.0 * et + 1e-6 * max(1.0, scale), (name, b, en, et)
+        else:
+            assert_close(got.cpu().numpy(), r64.cpu().numpy(), rtol=1e-3, atol_frac=2e-4, what=name)
+            en, et = float((got.double() - r64).abs().max()), float((t32.double() - r64).abs().max())
+            assert en <= 3.0 * et + 1e-7 * float(r64.abs().max()) + 1e-12, (name, en, et)
+    if edge == "zero_mask_image":                                      # image 1 sees no token: its code is the same for every token
+        assert bool((feats[1] == 0).all())
+        assert float((code[1] - code[1, :1]).abs().max()) == 0.0

@@ -203,3 +203,143 @@ def test_precompute_pipeline_native_backbone_to_neighbour_table():
     feats_ref = P.get_feats(model, loader)
     assert fz.backbone_path == "torch"
     assert float((feats - feats_ref).norm() / feats_ref.norm()) < 5e-3
+
+
+# ------------------------------------------------------------------------------------------------ GPU: every tile-kernel variant vs fp64
+def _clustered(n, d, seed, scale=1.0):
+    """Clustered fp32 rows on the device (64 centres + noise, as test_knn_vits8_width_8k_rows_against_oracle): L2-normalised when
+    scale is None, else raw rows times scale."""
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    centers = torch.randn(64, d, generator=g, device=DEV)
+    x = centers[torch.randint(0, 64, (n,), generator=g, device=DEV)] + 0.7 * torch.randn(n, d, generator=g, device=DEV)
+    return torch.nn.functional.normalize(x, dim=1).contiguous() if scale is None else (scale * x).contiguous()
+
+
+def _knn_vs_fp64(x, idx, sims, k, q_begin=0, normalize=False, rows_per_block=2048):
+    """The kernel's table against fp64 similarities computed on the device (row blocks of x64[q] @ x64^T), and torch fp32 (einsum +
+    topk) on the same data as the yardstick.  Checks validity / order / duplicates and returns the measured errors:
+      gap     max |s64[returned] - exact top-k s64|      (elementwise in rank order: only tie-band swaps may differ)
+      unsort  max s64[rank r + 1] - s64[rank r]
+      sim     max |returned sims - s64[returned]|
+      e32     max |s32 - s64| of torch fp32 over the same rows (all columns): the fp32 class of this data
+      gap32   the gap of torch fp32's own top-k"""
+    N = x.shape[0]
+    q = idx.shape[0]
+    assert idx.dtype == torch.int64 and tuple(idx.shape) == (q, k)
+    assert int(idx.min()) >= 0 and int(idx.max()) < N, "index out of [0, N) (or -1: an unfilled list slot)"
+    srt = torch.sort(idx, dim=1).values
+    assert bool((srt[:, 1:] > srt[:, :-1]).all()), "duplicate neighbour in a row"
+    x64 = x.double()
+    x32 = x
+    if normalize:                                                    # F.normalize, eps 1e-12 (precompute_knns.py:19)
+        x64 = torch.nn.functional.normalize(x64, dim=1, eps=1e-12)
+        x32 = torch.nn.functional.normalize(x, dim=1, eps=1e-12)
+    m = dict(gap=0.0, unsort=0.0, sim=0.0, e32=0.0, gap32=0.0)
+    for r0 in range(0, q, rows_per_block):
+        r1 = min(q, r0 + rows_per_block)
+        s = x64[q_begin + r0:q_begin + r1] @ x64.T
+        ref_val = torch.topk(s, k, dim=1).values
+        got = torch.gather(s, 1, idx[r0:r1])
+        s32 = torch.einsum("nf,mf->nm", x32[q_begin + r0:q_begin + r1], x32)
+        i32 = torch.topk(s32, k, dim=1).indices
+        m["gap"] = max(m["gap"], float((got - ref_val).abs().max()))
+        if k > 1:
+            m["unsort"] = max(m["unsort"], float((got[:, 1:] - got[:, :-1]).max()))
+        m["sim"] = max(m["sim"], float((sims[r0:r1].double() - got).abs().max()))
+        m["e32"] = max(m["e32"], float((s32.double() - s).abs().max()))
+        m["gap32"] = max(m["gap32"], float((torch.gather(s, 1, i32) - ref_val).abs().max()))
+    return m
+
+
+def _assert_fp32_class(m, what=""):
+    """The kernel's table is in the fp32 class of torch on the same data: its similarities err by at most 2 x torch fp32's largest
+    similarity error e32, so a returned neighbour can miss the exact top-k only inside a tie band of 2 x that, and its rank order can
+    be inverted only inside that band as well."""
+    band = 2.0 * (2.0 * m["e32"])
+    assert m["sim"] <= 2.0 * m["e32"], ("returned sims vs fp64", what, m)
+    assert m["gap"] <= max(band, m["gap32"]), ("top-k similarities vs fp64", what, m)
+    assert m["unsort"] <= band, ("neighbours not sorted by descending similarity", what, m)
+
+
+def _knn(x, k, **kw):
+    from stego_amd import capi
+    idx, sims = capi.knn_topk(x, k=k, return_sims=True, **kw)
+    torch.cuda.synchronize()
+    return idx, sims
+
+
+_WIDE = [(n, d, (1, 30, 32)[(i + j) % 3]) for i, n in enumerate((50, 129, 8192, 20000)) for j, d in enumerate((385, 448, 768, 1000))]
+
+
+# knn_tile_kernel<false> (both operands staged in LDS): launch_knn takes it when NCH = ceil(D / 64) > KNN_AREG_CHUNKS = 6, i.e. D > 384
+@gpu
+@pytest.mark.parametrize("n,d,k", _WIDE)
+def test_knn_wide_features_against_fp64(n, d, k):
+    """D in {385 (NCH = 7, the first width past the register path), 448 (whole chunks), 768 (ViT-B), 1000 (a partial last chunk)};
+    N = 8192 / 20000 cut every query block into several segments (at uneven places for 20000), merged by knn_merge_kernel."""
+    x = _clustered(n, d, seed=n + d, scale=None)
+    idx, sims = _knn(x, k)
+    m = _knn_vs_fp64(x, idx, sims, k)
+    _assert_fp32_class(m, (n, d, k))
+    assert torch.equal(idx[:, 0].cpu(), torch.arange(n)), "rank 0 is not the row itself"
+
+
+# both tile-kernel variants: knn_tile_kernel<true> at D = 384 (NCH = 6 <= KNN_AREG_CHUNKS), knn_tile_kernel<false> at D = 768 (NCH = 12)
+@gpu
+@pytest.mark.parametrize("d", [384, 768])
+def test_knn_normalize_with_zero_rows_against_fp64(d):
+    """normalize=True (F.normalize inside, eps 1e-12) on raw rows of varying norm, 7 of them all zero: the eps branch makes them zero
+    vectors whose similarity to everything is exactly 0."""
+    n, k = 1500, 30
+    x = _clustered(n, d, seed=d + 1, scale=3.0)
+    x *= torch.linspace(0.01, 40.0, n, device=DEV)[torch.randperm(n, generator=torch.Generator().manual_seed(2)).to(DEV)].unsqueeze(1)
+    zero = torch.tensor([0, 5, 127, 128, 700, 1401, n - 1], device=DEV)
+    x[zero] = 0.0
+    idx, sims = _knn(x, k, normalize=True)
+    m = _knn_vs_fp64(x, idx, sims, k, normalize=True)
+    _assert_fp32_class(m, d)
+    live = torch.ones(n, dtype=torch.bool, device=DEV)
+    live[zero] = False
+    assert torch.equal(idx[live, 0], torch.arange(n, device=DEV)[live])
+    assert bool((sims[zero] == 0).all()), "a zero row's similarities must be exactly 0"
+
+
+# both tile-kernel variants (D = 384: knn_tile_kernel<true>, D = 768: knn_tile_kernel<false>) reading rows ldx = x.stride(0) > D apart
+@gpu
+@pytest.mark.parametrize("d", [384, 768])
+def test_knn_strided_rows_and_query_slices_against_fp64(d):
+    """A column slice of a wider tensor (ldx = D + 37, first column 5: capi.knn_topk passes stride(0)), and query slices
+    (q_begin, q_count) that must equal the full table's rows bit for bit."""
+    n, k = 1100, 30
+    wide = _clustered(n, d + 37, seed=d + 2, scale=None)
+    x = wide[:, 5:5 + d]
+    assert x.stride(0) == d + 37 and x.stride(1) == 1
+    idx, sims = _knn(x, k, normalize=True)
+    m = _knn_vs_fp64(x.contiguous(), idx, sims, k, normalize=True)
+    _assert_fp32_class(m, d)
+    assert torch.equal(idx[:, 0].cpu(), torch.arange(n))
+    ref_idx, ref_sims = _knn(torch.nn.functional.normalize(x.contiguous(), dim=1), k)
+    for q0, qc in ((0, 128), (128, 300), (1024, 76), (256, 844)):
+        part, ps = _knn(x, k, normalize=True, q_begin=q0, q_count=qc)
+        assert torch.equal(part, idx[q0:q0 + qc]) and torch.equal(ps, sims[q0:q0 + qc]), (q0, qc)
+    mr = _knn_vs_fp64(torch.nn.functional.normalize(x.contiguous(), dim=1), ref_idx, ref_sims, k)
+    _assert_fp32_class(mr, (d, "dense"))
+
+
+# both tile-kernel variants (D = 384 / 768) on exact ties: a block of identical rows
+@gpu
+@pytest.mark.parametrize("d", [384, 768])
+def test_knn_duplicated_rows_against_fp64(d):
+    """40 copies of one row (exact ties at similarity 1 across two 128-row blocks): every returned similarity exact to the tie band,
+    indices valid and distinct, the first min(k, 40) neighbours of a copy are copies."""
+    n, k = 1000, 32
+    x = _clustered(n, d, seed=d + 3, scale=None)
+    dup = torch.arange(110, 150, device=DEV)
+    x[dup] = x[110].clone()
+    idx, sims = _knn(x, k)
+    m = _knn_vs_fp64(x, idx, sims, k)
+    _assert_fp32_class(m, d)
+    assert bool(torch.isin(idx[dup], dup).all()), "a copy's 32 best are not all copies"
+    rest = torch.ones(n, dtype=torch.bool, device=DEV)
+    rest[dup] = False
+    assert torch.equal(idx[rest, 0], torch.arange(n, device=DEV)[rest])

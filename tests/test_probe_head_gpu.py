@@ -61,6 +61,8 @@ CASES = [  # B, K, h, w, H, W, n_lin, n_clu, flip
     (2, 90, 20, 20, 160, 160, 3, 64, True),
     (1, 128, 17, 23, 136, 184, 64, 3, False),
     (2, 70, 12, 12, 96, 96, 28, 28, False),
+    (2, 70, 20, 20, 160, 160, 7, 5, True),          # probe_head_kernel<8>: the plan's NMAX is 8 when max(n_lin, n_clu) <= 8
+    (2, 32, 15, 17, 121, 135, 12, 16, False),       # probe_head_kernel<16>: 8 < max(n_lin, n_clu) <= 16
 ]
 
 
