@@ -83,6 +83,16 @@ PROBE_KINDS = {None: PROBE_SKIP, "log_probs": PROBE_LOG_PROBS, "probs": PROBE_PR
 PROBE_MAX_K, PROBE_MAX_N, PROBE_MAX_OUT = 128, 64, 2048
 
 
+class StegoPrDesc(Structure):
+    """include/stego_pr.h"""
+    _fields_ = [(n, c_int32) for n in ("B", "C", "h", "w", "HL", "WL", "N1", "N2", "n_bins", "n_classes", "flags")]
+
+
+PR_ERR_DIM, PR_ERR_POINTS, PR_ERR_BINS, PR_ERR_CLASSES, PR_ERR_SIZE, PR_ERR_FLAGS = 50, 51, 52, 53, 54, 55
+PR_RAW, PR_SKIP_UNLABELED = 1, 2
+PR_MAX_C, PR_MAX_POINTS, PR_MIN_BINS, PR_MAX_BINS, PR_MAX_CLASSES, PR_MAX_SIDE = 768, 4096, 64, 8192, 255, 16384
+
+
 _H = POINTER(StegoHeadDesc)
 _D = POINTER(StegoCorrDesc)
 _M = POINTER(StegoMap)
@@ -104,6 +114,8 @@ SIGNATURES = {
     "stego_data_prepare": (c_int32, [POINTER(StegoDataDesc)] + [_P] * 10 + [_P]),
     "stego_probe_head": (c_int32, [POINTER(StegoProbeDesc), _M, _M] + [_P] * 5 + [_P]),
     "stego_probe_head_plan": (c_size_t, [POINTER(StegoProbeDesc), POINTER(c_int32), POINTER(c_int32)]),
+    "stego_pr_accumulate": (c_int32, [POINTER(StegoPrDesc), _M, _M] + [_P] * 6 + [_P]),
+    "stego_pr_plan": (c_size_t, [POINTER(StegoPrDesc), POINTER(c_int32), POINTER(c_int32)]),
     "stego_abi_version": (c_int32, []),
     "stego_debug_set": (c_int32, [c_int32, c_int32]),
     "stego_debug_occupy": (c_int32, [c_int32, c_int32, c_int32, _P]),
@@ -1029,3 +1041,52 @@ def probe_head(code, code_flip, lin_w, lin_b, centroids, size, lin_kind, clu_kin
     with _on_device(dev):
         _check(probe_head_raw(desc, _map(code), _map(code_flip) if code_flip is not None else None, lw, lb, ce, lo, co, _stream()))
     return lo, co
+
+
+# ---- label co-occurrence PR histogram of feature correspondences (include/stego_pr.h; stego_amd.correspondence_pr wraps it)
+def pr_desc(B, C, h, w, HL, WL, N1, N2, n_bins, n_classes, flags=0):
+    return StegoPrDesc(int(B), int(C), int(h), int(w), int(HL), int(WL), int(N1), int(N2), int(n_bins), int(n_classes), int(flags))
+
+
+def pr_plan(desc):
+    """stego_pr_plan (host only) -> (LDS bytes, point tiles of coords1, point tiles of coords2); 0 bytes for an invalid descriptor."""
+    t1, t2 = c_int32(0), c_int32(0)
+    n = load().stego_pr_plan(byref(desc), byref(t1), byref(t2))
+    return int(n), t1.value, t2.value
+
+
+def pr_accumulate_raw(desc, a, b, labels_a, labels_b, index_b, coords1, coords2, hist, stream=None):
+    """stego_pr_accumulate with every argument given: `a` / `b` are StegoMap (or None), the rest raw addresses or tensors (tests: the
+    error codes) -> the return code, unchecked."""
+    def addr(x):
+        return _ptr(x) if torch.is_tensor(x) else x
+    return int(load().stego_pr_accumulate(byref(desc), byref(a) if a is not None else None, byref(b) if b is not None else None,
+                                          addr(labels_a), addr(labels_b), addr(index_b), addr(coords1), addr(coords2), addr(hist),
+                                          stream if stream is not None else None))
+
+
+def pr_accumulate(a, b, labels_a, labels_b, coords1, coords2, hist, n_classes, index_b=None, normalize=True, skip_unlabeled=False):
+    """stego_pr_accumulate: a, b float32 [B, C, h, w] (any strides), labels_a / labels_b integer [B, HL, WL], coords1 [B, N1, 2] or
+    [B, S, S, 2] and coords2 likewise, hist int64 [n_bins, 2] (negatives, positives), all on one HIP device.  Adds every pair
+    (point of coords1, point of coords2) of every image to `hist` in place and returns it; image i of `a` is paired with image
+    index_b[i] of `b` / `labels_b` (i itself without index_b)."""
+    _require_dev(a, b, labels_a, labels_b, coords1, coords2, hist, index_b)
+    if a.dim() != 4 or tuple(a.shape) != tuple(b.shape):
+        raise ValueError("pr_accumulate expects two float32 maps of one shape, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    B, C, h, w = a.shape
+    if labels_a.dim() != 3 or tuple(labels_a.shape) != tuple(labels_b.shape) or labels_a.shape[0] != B:
+        raise ValueError("pr_accumulate expects two [B, HL, WL] label maps, got %s and %s" % (tuple(labels_a.shape), tuple(labels_b.shape)))
+    if hist.dtype != torch.int64 or hist.dim() != 2 or hist.shape[1] != 2 or not hist.is_contiguous():
+        raise ValueError("pr_accumulate expects a contiguous int64 [n_bins, 2] histogram")
+    c1 = _dense(coords1.reshape(B, -1, 2), torch.float32)
+    c2 = _dense(coords2.reshape(B, -1, 2), torch.float32)
+    la, lb = _dense(labels_a, torch.int64), _dense(labels_b, torch.int64)
+    if index_b is not None:
+        index_b = _dense(index_b, torch.int64)
+        if index_b.numel() != B:
+            raise ValueError("index_b has %d entries for %d images" % (index_b.numel(), B))
+    flags = (0 if normalize else PR_RAW) | (PR_SKIP_UNLABELED if skip_unlabeled else 0)
+    desc = pr_desc(B, C, h, w, la.shape[1], la.shape[2], c1.shape[1], c2.shape[1], hist.shape[0], n_classes, flags)
+    with _on_device(a.device):
+        _check(pr_accumulate_raw(desc, _map(a), _map(b), la, lb, index_b, c1, c2, hist, _stream()))
+    return hist

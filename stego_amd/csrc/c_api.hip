@@ -10,6 +10,7 @@
 #include "../../include/stego_crf.h"
 #include "../../include/stego_data.h"
 #include "../../include/stego_probe.h"
+#include "../../include/stego_pr.h"
 #include "corr_wide.h"
 
 namespace stego {
@@ -367,6 +368,12 @@ const char* stego_error_string(int code)
         case STEGO_ERR_PROBE_DIM: return "probe head: K outside [1, 128] or an active probe's labels outside [1, 64] (include/stego_probe.h)";
         case STEGO_ERR_PROBE_SIZE: return "probe head: B outside [1, 65535], code side outside [1, 65535] or output side outside [1, 2048]";
         case STEGO_ERR_PROBE_OUTPUT: return "probe head: unknown output kind, or both probes skipped";
+        case STEGO_ERR_PR_DIM: return "correspondence PR: C outside [1, 768] (include/stego_pr.h)";
+        case STEGO_ERR_PR_POINTS: return "correspondence PR: N1 or N2 outside [1, 4096]";
+        case STEGO_ERR_PR_BINS: return "correspondence PR: n_bins outside [64, 8192]";
+        case STEGO_ERR_PR_CLASSES: return "correspondence PR: n_classes outside [1, 255]";
+        case STEGO_ERR_PR_SIZE: return "correspondence PR: B outside [1, 65535], or a map or label side outside [1, 16384]";
+        case STEGO_ERR_PR_FLAGS: return "correspondence PR: unknown flag bit";
         case STEGO_ERR_CRF_RANGE: return "dense CRF: a lattice coordinate would leave the packed key (image too large for its standard deviations)";
         default: return code >= STEGO_ERR_HIP ? "HIP runtime error (code - 1000 = hipError_t)" : "unknown error";
     }
