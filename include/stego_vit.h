@@ -31,10 +31,11 @@ typedef struct StegoVitDesc {
     int32_t B;        /* images per call                                                     */
     int32_t H, W;     /* image size, multiples of `patch`                                    */
     int32_t patch;    /* 8 or 16                     (vision_transformer.py:123-133)         */
-    int32_t D;        /* embed dim, multiple of 64:  192 / 384 / 768 (vit_tiny/small/base)   */
+    int32_t D;        /* embed dim: any multiple of 64 up to 768 (192 / 384 / 768 are        */
+                      /* vit_tiny/small/base; the others end in a partial column tile)       */
     int32_t depth;    /* blocks                                                              */
     int32_t heads;    /* D / heads must be 64                                                */
-    int32_t hidden;   /* MLP hidden width (4 * D), multiple of 64                            */
+    int32_t hidden;   /* MLP hidden width: any multiple of 64 (4 * D in the DINO models)     */
     int32_t precision;/* STEGO_VIT_F16 | STEGO_VIT_F16X3 (ABI 6); weights packed for one precision   */
                       /* are read by forwards of the same precision only                            */
 } StegoVitDesc;

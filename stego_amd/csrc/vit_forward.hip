@@ -218,8 +218,10 @@ __global__ void __launch_bounds__(256) vit_layernorm_kernel(const float* __restr
 }
 
 // ------------------------------------------------------------------------------------------------- GEMM
-// C[m][n] = sum_k A[m][k] W[n][k]  (+ epilogue): 256 x 192 tile per workgroup (every N of a ViT is a multiple of
-// 192 = 3 x 64), 8 waves as 4 x 2, each 64 x 96 (2 x 3 MFMA blocks, 96 accumulator registers), fp16 operands on
+// C[m][n] = sum_k A[m][k] W[n][k]  (+ epilogue): 256 x 192 tile per workgroup (every N of a DINO ViT is a multiple of
+// 192 = 3 x 64; check_desc takes every multiple of 64: the last column tile is then partial - wpanels() pads the weight
+// panels with zero rows to whole tiles and the epilogues skip n >= N / kc >= out_nkc, tests/test_vit_edges.py),
+// 8 waves as 4 x 2, each 64 x 96 (2 x 3 MFMA blocks, 96 accumulator registers), fp16 operands on
 // v_mfma_f32_32x32x16_f16, fp32 accumulate.  Both operands arrive as panels, so one 64-deep k stage is five linear
 // LDS-DMA copies (two A panels + 192 W rows, 63 KiB), double buffered: 126 KiB of LDS, one workgroup per CU.
 // The first version used 128 x 128 tiles (64 flop per staged byte): its k loop ran at the latency of the copies
