@@ -93,6 +93,15 @@ PR_RAW, PR_SKIP_UNLABELED = 1, 2
 PR_MAX_C, PR_MAX_POINTS, PR_MIN_BINS, PR_MAX_BINS, PR_MAX_CLASSES, PR_MAX_SIDE = 768, 4096, 64, 8192, 255, 16384
 
 
+class StegoProbeTrainDesc(Structure):
+    """include/stego_probe_train.h"""
+    _fields_ = [(n, c_int32) for n in ("B", "K", "h", "w", "H", "W", "n_lin", "n_clu")]
+
+
+PTRAIN_ERR_DIM, PTRAIN_ERR_SIZE, PTRAIN_ERR_PROBES = 60, 61, 62
+PTRAIN_MAX_K, PTRAIN_MAX_N, PTRAIN_MAX_OUT, PTRAIN_MAX_CODE = 128, 64, 2048, 65535
+
+
 _H = POINTER(StegoHeadDesc)
 _D = POINTER(StegoCorrDesc)
 _M = POINTER(StegoMap)
@@ -116,6 +125,9 @@ SIGNATURES = {
     "stego_probe_head_plan": (c_size_t, [POINTER(StegoProbeDesc), POINTER(c_int32), POINTER(c_int32)]),
     "stego_pr_accumulate": (c_int32, [POINTER(StegoPrDesc), _M, _M] + [_P] * 6 + [_P]),
     "stego_pr_plan": (c_size_t, [POINTER(StegoPrDesc), POINTER(c_int32), POINTER(c_int32)]),
+    "stego_probe_train_workspace_bytes": (c_size_t, [POINTER(StegoProbeTrainDesc)]),
+    "stego_probe_train": (c_int32, [POINTER(StegoProbeTrainDesc), _M] + [_P] * 9 + [_P, c_size_t, _P]),
+    "stego_probe_train_plan": (c_size_t, [POINTER(StegoProbeTrainDesc), POINTER(c_int32)]),
     "stego_abi_version": (c_int32, []),
     "stego_debug_set": (c_int32, [c_int32, c_int32]),
     "stego_debug_occupy": (c_int32, [c_int32, c_int32, c_int32, _P]),
@@ -1041,6 +1053,73 @@ def probe_head(code, code_flip, lin_w, lin_b, centroids, size, lin_kind, clu_kin
     with _on_device(dev):
         _check(probe_head_raw(desc, _map(code), _map(code_flip) if code_flip is not None else None, lw, lb, ce, lo, co, _stream()))
     return lo, co
+
+
+# ---- fused training tail of the two probes (include/stego_probe_train.h; stego_amd.probe_train wraps it for the trainer)
+def probe_train_desc(B, K, h, w, H, W, n_lin, n_clu):
+    return StegoProbeTrainDesc(int(B), int(K), int(h), int(w), int(H), int(W), int(n_lin), int(n_clu))
+
+
+def probe_train_plan(desc):
+    """stego_probe_train_plan (host only) -> (LDS bytes per workgroup, workgroups of the main kernel); 0 bytes for an invalid descriptor."""
+    wgs = c_int32(0)
+    n = load().stego_probe_train_plan(byref(desc), byref(wgs))
+    return int(n), wgs.value
+
+
+def probe_train_workspace_bytes(desc):
+    return int(load().stego_probe_train_workspace_bytes(byref(desc)))
+
+
+def probe_train_raw(desc, code, label, lin_w, lin_b, clusters, losses, n_valid, d_lin_w, d_lin_b, d_clusters, workspace, workspace_bytes,
+                    stream=None):
+    """stego_probe_train with every argument given: `code` is a StegoMap (or None), the rest raw addresses or tensors (tests: the error
+    codes) -> the return code, unchecked."""
+    def addr(x):
+        return _ptr(x) if torch.is_tensor(x) else x
+    return int(load().stego_probe_train(byref(desc), byref(code) if code is not None else None, addr(label), addr(lin_w), addr(lin_b),
+                                        addr(clusters), addr(losses), addr(n_valid), addr(d_lin_w), addr(d_lin_b), addr(d_clusters),
+                                        addr(workspace), int(workspace_bytes), stream if stream is not None else None))
+
+
+def probe_train(code, label, lin_w, lin_b, clusters):
+    """stego_probe_train: code float32 [B, K, h, w] with any strides, label int64 [B, H, W], lin_w [n_lin, K], lin_b [n_lin], clusters
+    [n_clu, K] (not normalised) on one HIP device -> (losses float32 [2] (linear, cluster), n_valid int64 [1], d_lin_w, d_lin_b,
+    d_clusters).  A probe whose weights are None is skipped: its loss slot stays 0 and its gradients are None."""
+    _require_dev(code, label, lin_w, lin_b, clusters)
+    B, K, h, w = code.shape
+    lin, clu = lin_w is not None, clusters is not None
+    dev = code.device
+    n_lin = int(lin_w.shape[0]) if lin else 0
+    n_clu = int(clusters.shape[0]) if clu else 0
+    if lin:
+        if label.dtype != torch.int64 or label.dim() != 3 or label.shape[0] != B:
+            raise ValueError("probe_train expects an int64 [B, H, W] label map, got %s %s" % (label.dtype, tuple(label.shape)))
+        label = _dense(label, torch.int64)
+        H, W = int(label.shape[1]), int(label.shape[2])
+        lin_w, lin_b = _dense(lin_w.reshape(n_lin, -1), torch.float32), _dense(lin_b, torch.float32)
+        if tuple(lin_w.shape) != (n_lin, K) or tuple(lin_b.shape) != (n_lin,):
+            raise ValueError("linear probe %s / %s does not match K = %d" % (tuple(lin_w.shape), tuple(lin_b.shape), K))
+    else:
+        H, W, label = h, w, None
+    if clu:
+        clusters = _dense(clusters, torch.float32)
+        if tuple(clusters.shape) != (n_clu, K):
+            raise ValueError("clusters %s do not match K = %d" % (tuple(clusters.shape), K))
+    desc = probe_train_desc(B, K, h, w, H, W, n_lin, n_clu)
+    losses = torch.zeros(2, dtype=torch.float32, device=dev)
+    n_valid = torch.empty(1, dtype=torch.int64, device=dev)
+    d_lin_w = torch.empty(n_lin, K, dtype=torch.float32, device=dev) if lin else None
+    d_lin_b = torch.empty(n_lin, dtype=torch.float32, device=dev) if lin else None
+    d_clusters = torch.empty(n_clu, K, dtype=torch.float32, device=dev) if clu else None
+    n = probe_train_workspace_bytes(desc)
+    if n == 0:
+        _check(probe_train_raw(desc, _map(code), label, lin_w, lin_b, clusters, losses, n_valid, d_lin_w, d_lin_b, d_clusters, None, 0))
+    ws = _empty_bytes(n, dev)
+    with _on_device(dev):
+        _check(probe_train_raw(desc, _map(code), label, lin_w, lin_b, clusters, losses, n_valid, d_lin_w, d_lin_b, d_clusters, ws, n,
+                               _stream()))
+    return losses, n_valid, d_lin_w, d_lin_b, d_clusters
 
 
 # ---- label co-occurrence PR histogram of feature correspondences (include/stego_pr.h; stego_amd.correspondence_pr wraps it)

@@ -11,6 +11,7 @@
 #include "../../include/stego_data.h"
 #include "../../include/stego_probe.h"
 #include "../../include/stego_pr.h"
+#include "../../include/stego_probe_train.h"
 #include "corr_wide.h"
 
 namespace stego {
@@ -368,6 +369,9 @@ const char* stego_error_string(int code)
         case STEGO_ERR_PROBE_DIM: return "probe head: K outside [1, 128] or an active probe's labels outside [1, 64] (include/stego_probe.h)";
         case STEGO_ERR_PROBE_SIZE: return "probe head: B outside [1, 65535], code side outside [1, 65535] or output side outside [1, 2048]";
         case STEGO_ERR_PROBE_OUTPUT: return "probe head: unknown output kind, or both probes skipped";
+        case STEGO_ERR_PTRAIN_DIM: return "probe training: K outside [1, 128] or a probe's labels outside [0, 64] (include/stego_probe_train.h)";
+        case STEGO_ERR_PTRAIN_SIZE: return "probe training: B outside [1, 65535], code side outside [1, 65535] or label side outside [1, 2048]";
+        case STEGO_ERR_PTRAIN_PROBES: return "probe training: both probes skipped (n_lin == 0 and n_clu == 0)";
         case STEGO_ERR_PR_DIM: return "correspondence PR: C outside [1, 768] (include/stego_pr.h)";
         case STEGO_ERR_PR_POINTS: return "correspondence PR: N1 or N2 outside [1, 4096]";
         case STEGO_ERR_PR_BINS: return "correspondence PR: n_bins outside [64, 8192]";

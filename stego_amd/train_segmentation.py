@@ -24,6 +24,7 @@ import yaml
 from . import ddp
 from .featurizers import ClusterLookup, ContrastiveCRFLoss, DinoFeaturizer, FeaturePyramidNet
 from .modules import ContrastiveCorrelationLoss, norm, sample
+from .probe_train import probe_losses, torch_probe_losses
 from .utils import UnsupervisedMetrics, one_hot_feats, prep_args, resize
 
 
@@ -263,18 +264,12 @@ class LitUnsupervisedSegmenter(nn.Module):
             self.log('loss/crf', crf, **log_args)
             loss += cfg.crf_weight * crf
 
-        detached_code = torch.clone(code.detach())
-        linear_logits = self.linear_probe(detached_code)
-        linear_logits = F.interpolate(linear_logits, label.shape[-2:], mode='bilinear', align_corners=False)
-        # train_segmentation.py:199-203 flattens to [pixels, classes], boolean-indexes the valid pixels (a host sync) and takes the mean
-        # cross-entropy.  The same number from the spatial form: invalid labels become ignore_index, the mean runs over the rest - no
-        # sync, no 170 MB permute / gather, and the 2-D NLL kernels instead of the one-block reduction ATen runs on [1.6 M, 27] (7 of the
-        # 9 ms of a cached-backbone step, rocprofv3)
-        valid = (label >= 0) & (label < self.n_classes)
-        linear_loss = F.cross_entropy(linear_logits, torch.where(valid, label, torch.full_like(label, -100)), ignore_index=-100)
+        # train_segmentation.py:199-224: both probes train on the detached code.  cfg.native_probes: their losses and parameter
+        # gradients come from one fused call (include/stego_probe_train.h) instead of the torch chain
+        probes = probe_losses if getattr(cfg, "native_probes", False) else torch_probe_losses
+        linear_loss, cluster_loss = probes(code, label, self.linear_probe, self.cluster_probe)
         loss += linear_loss
         self.log('loss/linear', linear_loss, **log_args)
-        cluster_loss, _ = self.cluster_probe(detached_code, None)
         loss += cluster_loss
         self.log('loss/cluster', cluster_loss, **log_args)
         self.log('loss/total', loss, **log_args)
