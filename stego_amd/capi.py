@@ -102,6 +102,16 @@ PTRAIN_ERR_DIM, PTRAIN_ERR_SIZE, PTRAIN_ERR_PROBES = 60, 61, 62
 PTRAIN_MAX_K, PTRAIN_MAX_N, PTRAIN_MAX_OUT, PTRAIN_MAX_CODE = 128, 64, 2048, 65535
 
 
+class StegoHeatDesc(Structure):
+    """include/stego_heat.h"""
+    _fields_ = [(n, c_int32) for n in ("B", "C", "hs", "ws", "h", "w", "N", "H", "W", "flags")]
+
+
+HEAT_ERR_DIM, HEAT_ERR_POINTS, HEAT_ERR_SIZE, HEAT_ERR_OUTPUT, HEAT_ERR_FLAGS = 70, 71, 72, 73, 74
+HEAT_NO_CENTER, HEAT_NO_CLAMP = 1, 2
+HEAT_MAX_C, HEAT_MAX_POINTS, HEAT_MAX_SIDE, HEAT_MAX_CELLS, HEAT_MAX_OUT = 768, 4096, 16384, 16384, 2048
+
+
 _H = POINTER(StegoHeadDesc)
 _D = POINTER(StegoCorrDesc)
 _M = POINTER(StegoMap)
@@ -128,6 +138,9 @@ SIGNATURES = {
     "stego_probe_train_workspace_bytes": (c_size_t, [POINTER(StegoProbeTrainDesc)]),
     "stego_probe_train": (c_int32, [POINTER(StegoProbeTrainDesc), _M] + [_P] * 9 + [_P, c_size_t, _P]),
     "stego_probe_train_plan": (c_size_t, [POINTER(StegoProbeTrainDesc), POINTER(c_int32)]),
+    "stego_heat_workspace_bytes": (c_size_t, [POINTER(StegoHeatDesc)]),
+    "stego_heat_plan": (c_size_t, [POINTER(StegoHeatDesc), POINTER(c_int32), POINTER(c_int32), POINTER(c_size_t), POINTER(c_int32)]),
+    "stego_corr_heatmaps": (c_int32, [POINTER(StegoHeatDesc), _M, _M] + [_P] * 5 + [_P, c_size_t, _P]),
     "stego_abi_version": (c_int32, []),
     "stego_debug_set": (c_int32, [c_int32, c_int32]),
     "stego_debug_occupy": (c_int32, [c_int32, c_int32, c_int32, _P]),
@@ -1169,3 +1182,77 @@ def pr_accumulate(a, b, labels_a, labels_b, coords1, coords2, hist, n_classes, i
     with _on_device(a.device):
         _check(pr_accumulate_raw(desc, _map(a), _map(b), la, lb, index_b, c1, c2, hist, _stream()))
     return hist
+
+
+# ---- query-point correspondence heatmaps (include/stego_heat.h; stego_amd.correspondence_heatmaps wraps it)
+def heat_desc(B, C, hs, ws, h, w, N, H, W, flags=0):
+    return StegoHeatDesc(int(B), int(C), int(hs), int(ws), int(h), int(w), int(N), int(H), int(W), int(flags))
+
+
+def heat_workspace_bytes(desc):
+    return int(load().stego_heat_workspace_bytes(byref(desc)))
+
+
+def heat_plan(desc):
+    """stego_heat_plan (host only) -> (LDS bytes of the first launch, its grid, the second launch's grid, its LDS bytes, its output
+    rows per workgroup); 0 bytes for an invalid descriptor."""
+    g1, g2, lds2, rows = (c_int32 * 3)(), (c_int32 * 3)(), c_size_t(0), c_int32(0)
+    n = load().stego_heat_plan(byref(desc), g1, g2, byref(lds2), byref(rows))
+    return int(n), tuple(g1), tuple(g2), int(lds2.value), rows.value
+
+
+def heat_workspace_views(desc, ws):
+    """The four arrays of the workspace of a finished call (include/stego_heat.h) as views of the uint8 tensor `ws`:
+    psum float64 [B, N, NCH], low float32 [B, N, h, w], pmax float32 [B, N, NCH], pidx int32 [B, N, NCH]."""
+    rows, hw = desc.B * desc.N, desc.h * desc.w
+    nch = -(-hw // 128)
+    o1 = rows * nch * 8
+    o2 = o1 + rows * hw * 4
+    o3 = o2 + rows * nch * 4
+    return (ws[:o1].view(torch.float64).view(desc.B, desc.N, nch), ws[o1:o2].view(torch.float32).view(desc.B, desc.N, desc.h, desc.w),
+            ws[o2:o3].view(torch.float32).view(desc.B, desc.N, nch), ws[o3:o3 + rows * nch * 4].view(torch.int32).view(desc.B, desc.N, nch))
+
+
+def corr_heatmaps_raw(desc, src, tgt, index_t, points, heat, peak, best, workspace, workspace_bytes, stream=None):
+    """stego_corr_heatmaps with every argument given: `src` / `tgt` are StegoMap (or None), the rest raw addresses or tensors (tests:
+    the error codes) -> the return code, unchecked."""
+    def addr(x):
+        return _ptr(x) if torch.is_tensor(x) else x
+    return int(load().stego_corr_heatmaps(byref(desc), byref(src) if src is not None else None, byref(tgt) if tgt is not None else None,
+                                          addr(index_t), addr(points), addr(heat), addr(peak), addr(best), addr(workspace),
+                                          int(workspace_bytes), stream if stream is not None else None))
+
+
+def corr_heatmaps(src, tgt, points, size, center=True, clamp=True, index_t=None, want_best=False, keep_workspace=False):
+    """stego_corr_heatmaps: src float32 [B, C, hs, ws], tgt float32 [B, C, h, w] (any strides), points [B, N, 2] or [B, N, 1, 2] as
+    (x, y) in [-1, 1], index_t int64 [B] or None, all on one HIP device -> heat float32 [B, N, H, W] for size = (H, W); with want_best
+    also peak [B, N] and best [B, N, 2]; with keep_workspace also (desc, workspace) for capi.heat_workspace_views."""
+    _require_dev(src, tgt, points, index_t)
+    if src.dim() != 4 or tgt.dim() != 4 or src.shape[:2] != tgt.shape[:2]:
+        raise ValueError("corr_heatmaps expects two float32 maps [B, C, ., .] of one B and C, got %s and %s" % (tuple(src.shape), tuple(tgt.shape)))
+    B, C, hs, ws_ = src.shape
+    h, w = int(tgt.shape[2]), int(tgt.shape[3])
+    if points.shape[0] != B or points.shape[-1] != 2:
+        raise ValueError("corr_heatmaps expects points [B, N, 2] or [B, N, 1, 2], got %s" % (tuple(points.shape),))
+    pts = _dense(points.reshape(B, -1, 2), torch.float32)
+    N = int(pts.shape[1])
+    H, W = int(size[0]), int(size[1])
+    if index_t is not None:
+        index_t = _dense(index_t, torch.int64)
+        if index_t.numel() != B:
+            raise ValueError("index_t has %d entries for %d images" % (index_t.numel(), B))
+    desc = heat_desc(B, C, hs, ws_, h, w, N, H, W, (0 if center else HEAT_NO_CENTER) | (0 if clamp else HEAT_NO_CLAMP))
+    dev = src.device
+    n = heat_workspace_bytes(desc)
+    if n == 0:
+        _check(corr_heatmaps_raw(desc, _map(src), _map(tgt), index_t, pts, 16, None, None, None, 0))      # raises with the descriptor's code
+    heat = torch.empty(B, N, H, W, dtype=torch.float32, device=dev)
+    peak = torch.empty(B, N, dtype=torch.float32, device=dev) if want_best else None
+    best = torch.empty(B, N, 2, dtype=torch.float32, device=dev) if want_best else None
+    ws = _empty_bytes(n, dev)
+    with _on_device(dev):
+        _check(corr_heatmaps_raw(desc, _map(src), _map(tgt), index_t, pts, heat, peak, best, ws, n, _stream()))
+    out = (heat, peak, best) if want_best else heat
+    if keep_workspace:
+        return out, desc, ws
+    return out

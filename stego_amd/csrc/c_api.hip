@@ -12,6 +12,7 @@
 #include "../../include/stego_probe.h"
 #include "../../include/stego_pr.h"
 #include "../../include/stego_probe_train.h"
+#include "../../include/stego_heat.h"
 #include "corr_wide.h"
 
 namespace stego {
@@ -378,6 +379,11 @@ const char* stego_error_string(int code)
         case STEGO_ERR_PR_CLASSES: return "correspondence PR: n_classes outside [1, 255]";
         case STEGO_ERR_PR_SIZE: return "correspondence PR: B outside [1, 65535], or a map or label side outside [1, 16384]";
         case STEGO_ERR_PR_FLAGS: return "correspondence PR: unknown flag bit";
+        case STEGO_ERR_HEAT_DIM: return "correspondence heatmaps: C outside [1, 768] (include/stego_heat.h)";
+        case STEGO_ERR_HEAT_POINTS: return "correspondence heatmaps: N outside [1, 4096]";
+        case STEGO_ERR_HEAT_SIZE: return "correspondence heatmaps: B outside [1, 65535], a source side outside [1, 16384], or a target map of no or more than 16384 cells";
+        case STEGO_ERR_HEAT_OUTPUT: return "correspondence heatmaps: output side outside [1, 2048]";
+        case STEGO_ERR_HEAT_FLAGS: return "correspondence heatmaps: unknown flag bit";
         case STEGO_ERR_CRF_RANGE: return "dense CRF: a lattice coordinate would leave the packed key (image too large for its standard deviations)";
         default: return code >= STEGO_ERR_HIP ? "HIP runtime error (code - 1000 = hipError_t)" : "unknown error";
     }
