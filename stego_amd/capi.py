@@ -112,6 +112,17 @@ HEAT_NO_CENTER, HEAT_NO_CLAMP = 1, 2
 HEAT_MAX_C, HEAT_MAX_POINTS, HEAT_MAX_SIDE, HEAT_MAX_CELLS, HEAT_MAX_OUT = 768, 4096, 16384, 16384, 2048
 
 
+class StegoCrfLossDesc(Structure):
+    """include/stego_crf_loss.h"""
+    _fields_ = [(n, c_int32) for n in ("B", "K", "G", "h", "w", "hg", "wg", "H", "W", "N")] + \
+               [(n, c_float) for n in ("alpha", "beta", "gamma", "w1", "w2", "shift")] + [("flags", c_int32)]
+
+
+CRFLOSS_ERR_DIM, CRFLOSS_ERR_POINTS, CRFLOSS_ERR_SIZE, CRFLOSS_ERR_PARAM, CRFLOSS_ERR_FLAGS = 80, 81, 82, 83, 84
+CRFLOSS_NORMALIZE = 1
+CRFLOSS_MAX_K, CRFLOSS_MAX_G, CRFLOSS_MAX_POINTS, CRFLOSS_MAX_SIDE, CRFLOSS_LAUNCHES = 128, 8, 4096, 2048, 3
+
+
 _H = POINTER(StegoHeadDesc)
 _D = POINTER(StegoCorrDesc)
 _M = POINTER(StegoMap)
@@ -141,6 +152,9 @@ SIGNATURES = {
     "stego_heat_workspace_bytes": (c_size_t, [POINTER(StegoHeatDesc)]),
     "stego_heat_plan": (c_size_t, [POINTER(StegoHeatDesc), POINTER(c_int32), POINTER(c_int32), POINTER(c_size_t), POINTER(c_int32)]),
     "stego_corr_heatmaps": (c_int32, [POINTER(StegoHeatDesc), _M, _M] + [_P] * 5 + [_P, c_size_t, _P]),
+    "stego_crf_loss_workspace_bytes": (c_size_t, [POINTER(StegoCrfLossDesc)]),
+    "stego_crf_loss_plan": (c_int32, [POINTER(StegoCrfLossDesc), POINTER(c_size_t), POINTER(c_int64)]),
+    "stego_crf_loss": (c_int32, [POINTER(StegoCrfLossDesc), _M, _M, _P, _P, _P, _M, _P, c_size_t, _P]),
     "stego_abi_version": (c_int32, []),
     "stego_debug_set": (c_int32, [c_int32, c_int32]),
     "stego_debug_occupy": (c_int32, [c_int32, c_int32, c_int32, _P]),
@@ -1256,3 +1270,63 @@ def corr_heatmaps(src, tgt, points, size, center=True, clamp=True, index_t=None,
     if keep_workspace:
         return out, desc, ws
     return out
+
+
+# ---- fused ContrastiveCRFLoss, forward and backward (include/stego_crf_loss.h; stego_amd.crf_loss wraps it for the trainer)
+def crf_loss_desc(B, K, G, h, w, hg, wg, H, W, N, alpha, beta, gamma, w1, w2, shift, flags=CRFLOSS_NORMALIZE):
+    return StegoCrfLossDesc(int(B), int(K), int(G), int(h), int(w), int(hg), int(wg), int(H), int(W), int(N), float(alpha), float(beta),
+                            float(gamma), float(w1), float(w2), float(shift), int(flags))
+
+
+def crf_loss_workspace_bytes(desc):
+    return int(load().stego_crf_loss_workspace_bytes(byref(desc)))
+
+
+def crf_loss_plan(desc):
+    """stego_crf_loss_plan (host only) -> (return code, [(LDS bytes, workgroups) of the prepare, pairs and finish launch])."""
+    lds, wgs = (c_size_t * CRFLOSS_LAUNCHES)(), (c_int64 * CRFLOSS_LAUNCHES)()
+    rc = load().stego_crf_loss_plan(byref(desc), lds, wgs)
+    return int(rc), [(int(a), int(b)) for a, b in zip(lds, wgs)]
+
+
+def crf_loss_raw(desc, guidance, code, coords, loss, per_image, d_code, workspace, workspace_bytes, stream=None):
+    """stego_crf_loss with every argument given: `guidance`, `code` and `d_code` are StegoMap (or None), the rest raw addresses or
+    tensors (tests: the error codes) -> the return code, unchecked."""
+    def addr(x):
+        return _ptr(x) if torch.is_tensor(x) else x
+
+    def ref(m):
+        return byref(m) if m is not None else None
+    return int(load().stego_crf_loss(byref(desc) if desc is not None else None, ref(guidance), ref(code), addr(coords), addr(loss),
+                                     addr(per_image), ref(d_code), addr(workspace), int(workspace_bytes),
+                                     stream if stream is not None else None))
+
+
+def crf_loss(guidance, code, coords, size, params, normalize=True, need_grad=True, want_per_image=True, d_code_like=None):
+    """stego_crf_loss: guidance float32 [B, G, hg, wg], code float32 [B, K, h, w] (any strides), coords int64 [2, N] (rows, columns) on
+    the grid size = (H, W), params = (alpha, beta, gamma, w1, w2, shift), all on one HIP device -> (loss float32 [1], per_image
+    float32 [B] or None, d_code float32 [B, K, h, w] for a unit upstream or None).  d_code takes the memory layout of `d_code_like`
+    (default: of the code).  The workspace comes from torch's caching allocator, as for the other fused calls."""
+    _require_dev(guidance, code, coords)
+    if guidance.dim() != 4 or code.dim() != 4 or guidance.shape[0] != code.shape[0]:
+        raise ValueError("crf_loss expects a guidance [B, G, ., .] and a code [B, K, ., .], got %s and %s"
+                         % (tuple(guidance.shape), tuple(code.shape)))
+    if coords.dim() != 2 or coords.shape[0] != 2:
+        raise ValueError("crf_loss expects coords [2, N], got %s" % (tuple(coords.shape),))
+    B, K, h, w = code.shape
+    G, hg, wg = guidance.shape[1:]
+    coords = _dense(coords, torch.int64)
+    dev = code.device
+    desc = crf_loss_desc(B, K, G, h, w, hg, wg, size[0], size[1], coords.shape[1], *params,
+                         flags=CRFLOSS_NORMALIZE if normalize else 0)
+    n = crf_loss_workspace_bytes(desc)
+    if n == 0:
+        _check(crf_loss_raw(desc, _map(guidance), _map(code), coords, 16, None, None, 16, 0))       # raises with the descriptor's code
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    per_image = torch.empty(B, dtype=torch.float32, device=dev) if want_per_image else None
+    d_code = torch.empty_like(code if d_code_like is None else d_code_like, dtype=torch.float32) if need_grad else None
+    ws = _empty_bytes(n, dev)
+    with _on_device(dev):
+        _check(crf_loss_raw(desc, _map(guidance), _map(code), coords, loss, per_image, _map(d_code) if need_grad else None, ws, n,
+                            _stream()))
+    return loss, per_image, d_code

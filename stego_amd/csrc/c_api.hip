@@ -13,6 +13,7 @@
 #include "../../include/stego_pr.h"
 #include "../../include/stego_probe_train.h"
 #include "../../include/stego_heat.h"
+#include "../../include/stego_crf_loss.h"
 #include "corr_wide.h"
 
 namespace stego {
@@ -384,6 +385,11 @@ const char* stego_error_string(int code)
         case STEGO_ERR_HEAT_SIZE: return "correspondence heatmaps: B outside [1, 65535], a source side outside [1, 16384], or a target map of no or more than 16384 cells";
         case STEGO_ERR_HEAT_OUTPUT: return "correspondence heatmaps: output side outside [1, 2048]";
         case STEGO_ERR_HEAT_FLAGS: return "correspondence heatmaps: unknown flag bit";
+        case STEGO_ERR_CRFLOSS_DIM: return "CRF loss: K outside [1, 128] or G outside [1, 8] (include/stego_crf_loss.h)";
+        case STEGO_ERR_CRFLOSS_POINTS: return "CRF loss: N outside [1, 4096]";
+        case STEGO_ERR_CRFLOSS_SIZE: return "CRF loss: B outside [1, 65535], or a side of the code, the guidance or the grid outside [1, 2048]";
+        case STEGO_ERR_CRFLOSS_PARAM: return "CRF loss: alpha, beta or gamma not finite and > 0, or w1, w2 or shift not finite";
+        case STEGO_ERR_CRFLOSS_FLAGS: return "CRF loss: unknown flag bit";
         case STEGO_ERR_CRF_RANGE: return "dense CRF: a lattice coordinate would leave the packed key (image too large for its standard deviations)";
         default: return code >= STEGO_ERR_HIP ? "HIP runtime error (code - 1000 = hipError_t)" : "unknown error";
     }

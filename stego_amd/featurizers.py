@@ -534,12 +534,29 @@ class ContrastiveCRFLoss(nn.Module):
         self.n_samples, self.alpha, self.beta, self.gamma = n_samples, alpha, beta, gamma
         self.w1, self.w2, self.shift = w1, w2, shift
 
+    def draw(self, h, w, device):
+        """The module's points: int64 [2, n_samples], rows then columns (the two randint calls of modules.py:456-458)."""
+        return torch.cat([torch.randint(0, h, size=[1, self.n_samples], device=device),
+                          torch.randint(0, w, size=[1, self.n_samples], device=device)], 0)
+
+    def mean_loss(self, guidance, code, size=None, normalize=False):
+        """forward(resize(guidance, size), [norm](resize(code, size))).mean() without the resized maps or a [B, N, N] tensor
+        (stego_amd.crf_loss.crf_mean_loss: one fused native call where it applies, the torch chain otherwise); size=None uses the
+        code's own resolution.  Draws the points exactly as forward does."""
+        from .crf_loss import crf_mean_loss
+        if size is None:
+            size = tuple(code.shape[2:])
+        elif isinstance(size, int):
+            size = (size, size)
+        coords = self.draw(size[0], size[1], code.device)
+        return crf_mean_loss(guidance, code, coords, size, (self.alpha, self.beta, self.gamma, self.w1, self.w2, self.shift),
+                             normalize=normalize)
+
     def forward(self, guidance, clusters):
         dev = clusters.device
         assert guidance.shape[0] == clusters.shape[0] and guidance.shape[2:] == clusters.shape[2:]
         h, w = guidance.shape[2], guidance.shape[3]
-        coords = torch.cat([torch.randint(0, h, size=[1, self.n_samples], device=dev),
-                            torch.randint(0, w, size=[1, self.n_samples], device=dev)], 0)
+        coords = self.draw(h, w, dev)
         g = guidance[:, :, coords[0], coords[1]]
         d_xy = (coords.unsqueeze(-1) - coords.unsqueeze(1)).square().sum(0).unsqueeze(0)
         d_g = (g.unsqueeze(-1) - g.unsqueeze(2)).square().sum(1)

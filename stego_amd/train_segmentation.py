@@ -260,7 +260,11 @@ class LitUnsupervisedSegmenter(nn.Module):
             loss += cfg.aug_alignment_weight * aug_alignment
 
         if cfg.crf_weight > 0:
-            crf = self.crf_loss_fn(resize(img, 56), norm(resize(code, 56))).mean()
+            if getattr(cfg, "native_crf_loss", False):
+                # the same number from one fused call that samples only the drawn points (include/stego_crf_loss.h)
+                crf = self.crf_loss_fn.mean_loss(img, code, size=56, normalize=True)
+            else:
+                crf = self.crf_loss_fn(resize(img, 56), norm(resize(code, 56))).mean()
             self.log('loss/crf', crf, **log_args)
             loss += cfg.crf_weight * crf
 
