@@ -123,6 +123,27 @@ CRFLOSS_NORMALIZE = 1
 CRFLOSS_MAX_K, CRFLOSS_MAX_G, CRFLOSS_MAX_POINTS, CRFLOSS_MAX_SIDE, CRFLOSS_LAUNCHES = 128, 8, 4096, 2048, 3
 
 
+class StegoAugParams(Structure):
+    """include/stego_aug.h: one image's draws (64 bytes)"""
+    _fields_ = [(n, c_int32) for n in ("flip", "top", "left", "ch", "cw")] + [("order", c_int32 * 4), ("factor", c_float * 4),
+                                                                              ("gray", c_int32), ("blur_sigma", c_float), ("reserved", c_int32)]
+
+
+class StegoAugDesc(Structure):
+    """include/stego_aug.h"""
+    _fields_ = [(n, c_int32) for n in ("B", "H", "W", "R")]
+
+
+class StegoAugAlignDesc(Structure):
+    """include/stego_aug.h"""
+    _fields_ = [(n, c_int32) for n in ("B", "K", "h", "w", "S", "Rh", "Rw")]
+
+
+AUG_ERR_SIZE, AUG_ERR_PARAM, AUGALIGN_ERR_DIM, AUGALIGN_ERR_SIZE = 90, 91, 92, 93
+AUG_BRIGHTNESS, AUG_CONTRAST, AUG_SATURATION, AUG_HUE, AUG_NONE = 0, 1, 2, 3, 4
+AUG_MAX_SIDE, AUG_MIN_RES, AUG_LAUNCHES, AUGALIGN_MAX_K, AUGALIGN_MAX_SIDE, AUGALIGN_LAUNCHES = 2048, 3, 2, 128, 256, 2
+
+
 _H = POINTER(StegoHeadDesc)
 _D = POINTER(StegoCorrDesc)
 _M = POINTER(StegoMap)
@@ -155,6 +176,13 @@ SIGNATURES = {
     "stego_crf_loss_workspace_bytes": (c_size_t, [POINTER(StegoCrfLossDesc)]),
     "stego_crf_loss_plan": (c_int32, [POINTER(StegoCrfLossDesc), POINTER(c_size_t), POINTER(c_int64)]),
     "stego_crf_loss": (c_int32, [POINTER(StegoCrfLossDesc), _M, _M, _P, _P, _P, _M, _P, c_size_t, _P]),
+    "stego_augment_check_params": (c_int32, [POINTER(StegoAugDesc), _P, POINTER(c_int64), POINTER(c_int32)]),
+    "stego_augment_workspace_bytes": (c_size_t, [POINTER(StegoAugDesc)]),
+    "stego_augment_plan": (c_int32, [POINTER(StegoAugDesc), POINTER(c_size_t), POINTER(c_int64)]),
+    "stego_augment": (c_int32, [POINTER(StegoAugDesc), _M, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "stego_aug_align_workspace_bytes": (c_size_t, [POINTER(StegoAugAlignDesc)]),
+    "stego_aug_align_plan": (c_int32, [POINTER(StegoAugAlignDesc), POINTER(c_size_t), POINTER(c_int64)]),
+    "stego_aug_align": (c_int32, [POINTER(StegoAugAlignDesc), _M, _M, _P, _P, _M, _M, _P, c_size_t, _P]),
     "stego_abi_version": (c_int32, []),
     "stego_debug_set": (c_int32, [c_int32, c_int32]),
     "stego_debug_occupy": (c_int32, [c_int32, c_int32, c_int32, _P]),
@@ -1330,3 +1358,125 @@ def crf_loss(guidance, code, coords, size, params, normalize=True, need_grad=Tru
         _check(crf_loss_raw(desc, _map(guidance), _map(code), coords, loss, per_image, _map(d_code) if need_grad else None, ws, n,
                             _stream()))
     return loss, per_image, d_code
+
+
+# ---- device-side augmented views and the fused aug-alignment loss (include/stego_aug.h; stego_amd.augment wraps them for the trainer)
+def _addr(x):
+    return _ptr(x) if torch.is_tensor(x) else x
+
+
+def _ref(m):
+    return byref(m) if m is not None else None
+
+
+def aug_desc(B, H, W, R):
+    return StegoAugDesc(int(B), int(H), int(W), int(R))
+
+
+def aug_check_params(desc, records):
+    """stego_augment_check_params (host only): `records` a ctypes array of StegoAugParams (or None) ->
+    (return code, index of the first bad record or -1, whether a record applies contrast)."""
+    bad, contrast = c_int64(-1), c_int32(0)
+    rc = load().stego_augment_check_params(byref(desc) if desc is not None else None,
+                                           ctypes.addressof(records) if records is not None else None, byref(bad), byref(contrast))
+    return int(rc), int(bad.value), bool(contrast.value)
+
+
+def augment_workspace_bytes(desc):
+    return int(load().stego_augment_workspace_bytes(byref(desc)))
+
+
+def augment_plan(desc):
+    """stego_augment_plan (host only) -> (return code, [(LDS bytes, workgroups) of the mean and the apply launch])."""
+    lds, wgs = (c_size_t * AUG_LAUNCHES)(), (c_int64 * AUG_LAUNCHES)()
+    rc = load().stego_augment_plan(byref(desc), lds, wgs)
+    return int(rc), [(int(a), int(b)) for a, b in zip(lds, wgs)]
+
+
+def augment_raw(desc, img, params_host, params, img_aug, coord_aug, workspace, workspace_bytes, stream=None):
+    """stego_augment with every argument given: `img` a StegoMap (or None), `params_host` a ctypes array of StegoAugParams, a raw
+    address or None, the rest raw addresses or tensors (tests: the error codes) -> the return code, unchecked."""
+    host = ctypes.addressof(params_host) if isinstance(params_host, ctypes.Array) else params_host
+    return int(load().stego_augment(byref(desc) if desc is not None else None, _ref(img), host, _addr(params), _addr(img_aug),
+                                    _addr(coord_aug), _addr(workspace), int(workspace_bytes), stream if stream is not None else None))
+
+
+def aug_table(records, dev):
+    """The B records as device bytes: one small copy from pinned memory on the current stream; nothing waits for the device."""
+    host = torch.frombuffer(bytearray(bytes(records)), dtype=torch.uint8).pin_memory()
+    return host.to(dev, non_blocking=True)
+
+
+def augment(img, records, R, table=None):
+    """stego_augment: img float32 [B, 3, H, W] on a HIP device (any strides), `records` a ctypes array of B StegoAugParams ->
+    (img_aug float32 [B, 3, R, R], coord_aug float32 [B, R, R, 2]).  `table`: aug_table(records, device) made earlier (a call that
+    is captured into a graph takes it from outside the capture); by default it is made here."""
+    _require_dev(img)
+    if img.dim() != 4 or img.shape[1] != 3:
+        raise ValueError("augment expects an image batch [B, 3, H, W], got %s" % (tuple(img.shape),))
+    B, _, H, W = img.shape
+    if len(records) != B:
+        raise ValueError("augment: %d parameter records for %d images" % (len(records), B))
+    dev = img.device
+    desc = aug_desc(B, H, W, R)
+    n = augment_workspace_bytes(desc)
+    if n == 0:
+        _check(augment_raw(desc, _map(img), records, 16, 16, 16, 16, 0))          # raises with the descriptor's code
+    img_aug = torch.empty(B, 3, R, R, dtype=torch.float32, device=dev)
+    coord_aug = torch.empty(B, R, R, 2, dtype=torch.float32, device=dev)
+    ws = _empty_bytes(n, dev)
+    with _on_device(dev):
+        if table is None:
+            table = aug_table(records, dev)
+        _check(augment_raw(desc, _map(img), records, table, img_aug, coord_aug, ws, n, _stream()))
+    return img_aug, coord_aug
+
+
+def aug_align_desc(B, K, h, w, S, Rh, Rw):
+    return StegoAugAlignDesc(int(B), int(K), int(h), int(w), int(S), int(Rh), int(Rw))
+
+
+def aug_align_workspace_bytes(desc):
+    return int(load().stego_aug_align_workspace_bytes(byref(desc)))
+
+
+def aug_align_plan(desc):
+    """stego_aug_align_plan (host only) -> (return code, [(LDS bytes, workgroups) of the pixels and the finish launch])."""
+    lds, wgs = (c_size_t * AUGALIGN_LAUNCHES)(), (c_int64 * AUGALIGN_LAUNCHES)()
+    rc = load().stego_aug_align_plan(byref(desc), lds, wgs)
+    return int(rc), [(int(a), int(b)) for a, b in zip(lds, wgs)]
+
+
+def aug_align_raw(desc, code, code_aug, coord, loss, d_code, d_code_aug, workspace, workspace_bytes, stream=None):
+    """stego_aug_align with every argument given: the four maps are StegoMap (or None), the rest raw addresses or tensors (tests: the
+    error codes) -> the return code, unchecked."""
+    return int(load().stego_aug_align(byref(desc) if desc is not None else None, _ref(code), _ref(code_aug), _addr(coord), _addr(loss),
+                                      _ref(d_code), _ref(d_code_aug), _addr(workspace), int(workspace_bytes),
+                                      stream if stream is not None else None))
+
+
+def aug_align(code, code_aug, coord, need_code=True, need_code_aug=True):
+    """stego_aug_align: code float32 [B, K, h, w] and code_aug float32 [B, K, S, S] (any strides), coord float32 [B, Rh, Rw, 2], all
+    on one HIP device -> (loss float32 [1], d_code or None, d_code_aug or None), the gradients for a unit upstream in the layout of
+    their inputs.  The workspace comes from torch's caching allocator, as for the other fused calls."""
+    _require_dev(code, code_aug, coord)
+    if code.dim() != 4 or code_aug.dim() != 4 or code_aug.shape[:2] != code.shape[:2] or code_aug.shape[2] != code_aug.shape[3]:
+        raise ValueError("aug_align expects a code [B, K, h, w] and a square code_aug [B, K, S, S], got %s and %s"
+                         % (tuple(code.shape), tuple(code_aug.shape)))
+    if coord.dim() != 4 or coord.shape[0] != code.shape[0] or coord.shape[3] != 2:
+        raise ValueError("aug_align expects coord [B, Rh, Rw, 2], got %s" % (tuple(coord.shape),))
+    B, K, h, w = code.shape
+    coord = _dense(coord, torch.float32)
+    dev = code.device
+    desc = aug_align_desc(B, K, h, w, code_aug.shape[2], coord.shape[1], coord.shape[2])
+    n = aug_align_workspace_bytes(desc)
+    if n == 0:
+        _check(aug_align_raw(desc, _map(code), _map(code_aug), coord, 16, None, None, 16, 0))       # raises with the descriptor's code
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    d_code = torch.empty_like(code) if need_code else None
+    d_code_aug = torch.empty_like(code_aug) if need_code_aug else None
+    ws = _empty_bytes(n, dev)
+    with _on_device(dev):
+        _check(aug_align_raw(desc, _map(code), _map(code_aug), coord, loss, _map(d_code) if need_code else None,
+                             _map(d_code_aug) if need_code_aug else None, ws, n, _stream()))
+    return loss, d_code, d_code_aug

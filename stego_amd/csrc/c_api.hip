@@ -14,6 +14,7 @@
 #include "../../include/stego_probe_train.h"
 #include "../../include/stego_heat.h"
 #include "../../include/stego_crf_loss.h"
+#include "../../include/stego_aug.h"
 #include "corr_wide.h"
 
 namespace stego {
@@ -390,6 +391,10 @@ const char* stego_error_string(int code)
         case STEGO_ERR_CRFLOSS_SIZE: return "CRF loss: B outside [1, 65535], or a side of the code, the guidance or the grid outside [1, 2048]";
         case STEGO_ERR_CRFLOSS_PARAM: return "CRF loss: alpha, beta or gamma not finite and > 0, or w1, w2 or shift not finite";
         case STEGO_ERR_CRFLOSS_FLAGS: return "CRF loss: unknown flag bit";
+        case STEGO_ERR_AUG_SIZE: return "augment: B outside [1, 65535], H or W outside [1, 2048] or R outside [3, 2048] (include/stego_aug.h)";
+        case STEGO_ERR_AUG_PARAM: return "augment: a record of the parameter table is invalid (flip, crop, order, factors, gray or blur_sigma; include/stego_aug.h)";
+        case STEGO_ERR_AUGALIGN_DIM: return "aug alignment: K outside [1, 128] (include/stego_aug.h)";
+        case STEGO_ERR_AUGALIGN_SIZE: return "aug alignment: B outside [1, 65535], a side of code or code_aug outside [1, 256], or a side of coord outside [1, 2048]";
         case STEGO_ERR_CRF_RANGE: return "dense CRF: a lattice coordinate would leave the packed key (image too large for its standard deviations)";
         default: return code >= STEGO_ERR_HIP ? "HIP runtime error (code - 1000 = hipError_t)" : "unknown error";
     }

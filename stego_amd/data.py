@@ -190,7 +190,9 @@ class ContrastiveSegDataset(Dataset):
     nns[ind][r] with r uniform in [1, num_neighbors] from the precomputed table {pytorch_data_dir}/nns/nns_{model_type}_{dataset}_
     {image_set}_{crop_type}_{res}.npz.  The random draws come in the reference's order: the item's own CroppedDataset seed (numpy),
     torch.randint for the neighbour rank, the positive's CroppedDataset seed, then one more numpy seed that reseeds python's and
-    torch's generators (what the reference's augmentations would draw from).  The img_aug / coord_aug augmentations are not built.
+    torch's generators (what the reference's augmentations would draw from).  The img_aug / coord_aug augmentations are not made
+    here: they are made on the device, from the batch, by stego_amd.augment (cfg.native_aug; device_data.DeviceContrastiveLoader's
+    aug=True, or training_step itself for batches of this loader).
 
     This is the CPU loader of train_segmentation when the split does not fit the device, and the oracle of
     device_data.DeviceContrastiveLoader."""

@@ -228,7 +228,9 @@ class DeviceContrastiveLoader:
 
     With a neighbour table `nns` (int64 [n, >= num_neighbors + 1], row i's neighbours by similarity, column 0 = i itself): the
     reference's training batches (data.py ContrastiveSegDataset with pos_images, pos_labels and mask): `ind`, `img`, `label`,
-    `mask`, `img_pos`, `ind_pos`, `label_pos`, `mask_pos`.  Epoch e visits epoch_indices(n, world, rank, seed, e) in batches of
+    `mask`, `img_pos`, `ind_pos`, `label_pos`, `mask_pos`, and with aug=True `img_aug` and `coord_aug`, the augmented view of the
+    anchors of the batch just prepared (stego_amd.augment: one more native call; `last_aug_params` holds its draws, which come from
+    a host generator seeded from (seed, rank) as well).  Epoch e visits epoch_indices(n, world, rank, seed, e) in batches of
     `batch_size` (the last incomplete batch dropped with drop_last) - DistributedSampler's order.  The positive of `ind` is
     nns[ind, r], r uniform in [1, num_neighbors] (data.py:524); with crop="random" every crop origin is uniform over the resized
     image (RandomCrop).  Both come from a device generator seeded from (seed, rank) at construction: two loaders built alike give
@@ -238,7 +240,8 @@ class DeviceContrastiveLoader:
     Without `nns`: the split in order, `img`, `label`, `mask`, `ind` (validation, the KNN precompute); rank and world are ignored.
     One stego_data_prepare launch per batch covers anchors and positives together."""
 
-    def __init__(self, store, nns=None, batch_size=16, num_neighbors=7, res=224, crop="center", seed=0, rank=0, world=1, drop_last=True):
+    def __init__(self, store, nns=None, batch_size=16, num_neighbors=7, res=224, crop="center", seed=0, rank=0, world=1, drop_last=True,
+                 aug=False):
         if crop not in ("center", "random"):
             raise ValueError("Unknown Cropper {}".format(crop))
         self.store, self.batch_size, self.num_neighbors, self.res, self.crop = store, int(batch_size), int(num_neighbors), int(res), crop
@@ -257,6 +260,11 @@ class DeviceContrastiveLoader:
         self.deterministic_items, self.n_cache_items, self.per_rank = crop == "center", n, True
         self.epoch = 0
         self.last_origin = None
+        self.last_aug_params = None
+        self._augmenter = None
+        if aug:
+            from .augment import Augmenter
+            self._augmenter = Augmenter(self.res, self.seed, self.rank)
         self._gen = torch.Generator(device=store.device)
         self._gen.manual_seed((self.seed * 1000003 + self.rank) & 0x7FFFFFFFFFFFFFFF)
         store.table(self.res)
@@ -300,5 +308,9 @@ class DeviceContrastiveLoader:
             img, label, mask = self.store.prepare(both, self.res, origin)
             self.last_origin = origin
             k = ind.numel()
-            yield dict(ind=ind, img=img[:k], label=label[:k], mask=mask[:k], img_pos=img[k:], ind_pos=ind_pos, label_pos=label[k:],
-                       mask_pos=mask[k:])
+            batch = dict(ind=ind, img=img[:k], label=label[:k], mask=mask[:k], img_pos=img[k:], ind_pos=ind_pos, label_pos=label[k:],
+                         mask_pos=mask[k:])
+            if self._augmenter is not None:
+                self._augmenter(batch)
+                self.last_aug_params = self._augmenter.last_params
+            yield batch

@@ -22,6 +22,7 @@ import torch.nn.functional as F
 import yaml
 
 from . import ddp
+from .augment import Augmenter, aug_alignment_loss, needs_torchvision
 from .featurizers import ClusterLookup, ContrastiveCRFLoss, DinoFeaturizer, FeaturePyramidNet
 from .modules import ContrastiveCorrelationLoss, norm, sample
 from .probe_train import probe_losses, torch_probe_losses
@@ -127,6 +128,7 @@ class LitUnsupervisedSegmenter(nn.Module):
         self.logged = {}
         self._optims = None
         self._reducer = None
+        self._augmenter = None
 
     # ---- checkpoints in the layout Lightning writes for the reference (train_segmentation.py:106 save_hyperparameters,
     #      :487 ModelCheckpoint) and that eval_segmentation.py:67 / demo_segmentation.py:41 read back with
@@ -190,6 +192,12 @@ class LitUnsupervisedSegmenter(nn.Module):
         self._reducer.broadcast_params(0)
         return self._reducer
 
+    def augmenter(self):
+        """The maker of img_aug / coord_aug for batches that lack them (cfg.native_aug), seeded from this process's rank."""
+        if self._augmenter is None:
+            self._augmenter = Augmenter(self.cfg.res, seed=0, rank=int(os.environ.get("RANK", "0")))
+        return self._augmenter
+
     def manual_backward(self, loss):
         """loss.backward() + the DDP gradient exchange (Lightning's manual_backward under accelerator='ddp',
         train_segmentation.py:227): ONE asynchronous averaged all-reduce of the flat bucket; wait_gradients() joins it."""
@@ -252,7 +260,16 @@ class LitUnsupervisedSegmenter(nn.Module):
             self.log('loss/rec', rec_loss, **log_args)
             loss += cfg.rec_weight * rec_loss
 
-        if cfg.aug_alignment_weight > 0:
+        if cfg.aug_alignment_weight > 0 and getattr(cfg, "native_aug", False):
+            # the view from the device-side augmentation when the loader did not make it (the synthetic and CPU loaders), and the
+            # term with both gradients from one fused call that writes no resized map and no sampled code (include/stego_aug.h)
+            if "img_aug" not in batch:
+                self.augmenter()(batch)
+            _, code_aug = self.net(batch["img_aug"])
+            aug_alignment = aug_alignment_loss(code, code_aug, batch["coord_aug"])
+            self.log('loss/aug_alignment', aug_alignment, **log_args)
+            loss += cfg.aug_alignment_weight * aug_alignment
+        elif cfg.aug_alignment_weight > 0:
             _, code_aug = self.net(batch["img_aug"])
             coord = resize(batch["coord_aug"].permute(0, 3, 1, 2), code_aug.shape[2]).permute(0, 2, 3, 1)
             aug_alignment = -torch.einsum("bkhw,bkhw->bhw", norm(sample(code, coord)), norm(code_aug)).mean()
@@ -496,7 +513,8 @@ def _real_loaders(cfg, trainer):
             if not os.path.exists(nns_path):
                 raise ValueError("could not find nn file {} please run precompute_knns".format(nns_path))
             loader = DeviceContrastiveLoader(store, np.load(nns_path)["nns"], cfg.batch_size, cfg.num_neighbors, cfg.res, crop=crop,
-                                             seed=0, rank=trainer.rank, world=trainer.world, drop_last=True)
+                                             seed=0, rank=trainer.rank, world=trainer.world, drop_last=True,
+                                             aug=cfg.aug_alignment_weight > 0 and getattr(cfg, "native_aug", False))
             print("training data: device store (%d crops, %.2f GB on the device)" % (len(store), store.nbytes / 1e9))
     else:
         print("training data: CPU loader (ContrastiveSegDataset, %d workers): cfg.device_dataset is off" % cfg.num_workers)
@@ -532,10 +550,9 @@ def my_app(cfg):
     n_classes = get_class_labels(cfg.dataset_name)
     root = getattr(cfg, "pytorch_data_dir", None)
     if root and os.path.exists(join(crop_dir(root, cfg.dataset_name, cfg.crop_type, cfg.crop_ratio), "img", "train")):
-        if cfg.aug_alignment_weight > 0:
-            raise ValueError("cfg.aug_alignment_weight = %s: the img_aug / coord_aug augmentations need torchvision's photometric "
-                             "transforms, which this build does not have; set aug_alignment_weight=0 to train on real data"
-                             % cfg.aug_alignment_weight)
+        refusal = needs_torchvision(cfg)
+        if refusal:
+            raise ValueError(refusal)
         import random
         import numpy as np
         random.seed(0)
