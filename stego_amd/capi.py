@@ -83,6 +83,23 @@ PROBE_KINDS = {None: PROBE_SKIP, "log_probs": PROBE_LOG_PROBS, "probs": PROBE_PR
 PROBE_MAX_K, PROBE_MAX_N, PROBE_MAX_OUT = 128, 64, 2048
 
 
+class StegoProbeConfusionDesc(Structure):
+    """include/stego_confusion.h"""
+    _fields_ = [(n, c_int32) for n in ("B", "K", "h", "w", "H", "W", "n_lin", "n_clu", "lin_on", "clu_on")] + \
+        [("alpha", c_float), ("n_classes", c_int32)]
+
+
+class StegoConfusionDesc(Structure):
+    """include/stego_confusion.h"""
+    _fields_ = [(n, c_int32) for n in ("B", "n", "H", "W", "n_classes", "pred_kind")]
+
+
+CONF_ERR_DIM, CONF_ERR_SIZE, CONF_ERR_PROBES, CONF_ERR_KIND = 100, 101, 102, 103
+CONF_LABELS, CONF_SCORES = 0, 1
+CONF_KINDS = {"labels": CONF_LABELS, "scores": CONF_SCORES}
+CONF_MAX_N, CONF_MAX_PIXELS = 64, 1 << 40
+
+
 class StegoPrDesc(Structure):
     """include/stego_pr.h"""
     _fields_ = [(n, c_int32) for n in ("B", "C", "h", "w", "HL", "WL", "N1", "N2", "n_bins", "n_classes", "flags")]
@@ -165,6 +182,9 @@ SIGNATURES = {
     "stego_data_prepare": (c_int32, [POINTER(StegoDataDesc)] + [_P] * 10 + [_P]),
     "stego_probe_head": (c_int32, [POINTER(StegoProbeDesc), _M, _M] + [_P] * 5 + [_P]),
     "stego_probe_head_plan": (c_size_t, [POINTER(StegoProbeDesc), POINTER(c_int32), POINTER(c_int32)]),
+    "stego_probe_confusion": (c_int32, [POINTER(StegoProbeConfusionDesc), _M, _M] + [_P] * 6 + [_P]),
+    "stego_probe_confusion_plan": (c_size_t, [POINTER(StegoProbeConfusionDesc), POINTER(c_int32), POINTER(c_int32)]),
+    "stego_confusion": (c_int32, [POINTER(StegoConfusionDesc), _P, _P, _P, _P]),
     "stego_pr_accumulate": (c_int32, [POINTER(StegoPrDesc), _M, _M] + [_P] * 6 + [_P]),
     "stego_pr_plan": (c_size_t, [POINTER(StegoPrDesc), POINTER(c_int32), POINTER(c_int32)]),
     "stego_probe_train_workspace_bytes": (c_size_t, [POINTER(StegoProbeTrainDesc)]),
@@ -1108,6 +1128,110 @@ def probe_head(code, code_flip, lin_w, lin_b, centroids, size, lin_kind, clu_kin
     with _on_device(dev):
         _check(probe_head_raw(desc, _map(code), _map(code_flip) if code_flip is not None else None, lw, lb, ce, lo, co, _stream()))
     return lo, co
+
+
+# ---- device-side confusion matrices (include/stego_confusion.h; stego_amd.metrics wraps them for the trainer and evaluate())
+def probe_confusion_desc(B, K, h, w, H, W, n_lin, n_clu, lin_on, clu_on, alpha, n_classes):
+    return StegoProbeConfusionDesc(int(B), int(K), int(h), int(w), int(H), int(W), int(n_lin), int(n_clu), int(lin_on), int(clu_on),
+                                   float(alpha), int(n_classes))
+
+
+def confusion_desc(B, n, H, W, n_classes, pred_kind):
+    return StegoConfusionDesc(int(B), int(n), int(H), int(W), int(n_classes), int(pred_kind))
+
+
+def probe_confusion_plan(desc):
+    """stego_probe_confusion_plan (host only) -> (LDS bytes, histograms included; tile rows; tile columns); 0 bytes for an invalid
+    descriptor."""
+    ty, tx = c_int32(0), c_int32(0)
+    n = load().stego_probe_confusion_plan(byref(desc), byref(ty), byref(tx))
+    return int(n), ty.value, tx.value
+
+
+def _addr(x):
+    return _ptr(x) if torch.is_tensor(x) else x
+
+
+def probe_confusion_raw(desc, code, code_flip, lin_w, lin_b, centroids, labels, lin_counts, clu_counts, stream=None):
+    """stego_probe_confusion with every argument given: `code` / `code_flip` are StegoMap (or None), the rest raw addresses or
+    tensors (tests: the error codes) -> the return code, unchecked."""
+    return int(load().stego_probe_confusion(byref(desc) if desc is not None else None, byref(code) if code is not None else None,
+                                            byref(code_flip) if code_flip is not None else None, _addr(lin_w), _addr(lin_b),
+                                            _addr(centroids), _addr(labels), _addr(lin_counts), _addr(clu_counts),
+                                            stream if stream is not None else None))
+
+
+def _counts_ok(counts, n, n_classes, name):
+    if counts.dtype != torch.int64 or tuple(counts.shape) != (n, n_classes) or not counts.is_contiguous():
+        raise ValueError("%s: expected a contiguous int64 [%d, %d] tensor, got %s %s" % (name, n, n_classes, counts.dtype, tuple(counts.shape)))
+
+
+def probe_confusion(code, code_flip, lin_w, lin_b, centroids, labels, lin_counts, clu_counts, alpha):
+    """stego_probe_confusion: code (and code_flip, or None) float32 [B, K, h, w] with any strides, labels int64 [B, H, W], and per
+    probe its weights (lin_w [n_lin, K] and lin_b [n_lin]; centroids [n_clu, K], L2-normalised) and its int64 [n, n_classes] matrix,
+    which is added onto in place.  A probe whose counts are None is skipped; n_classes is the counts' second dimension.  Nothing is
+    returned and nothing synchronises."""
+    if lin_counts is None and clu_counts is None:
+        raise ValueError("probe_confusion: both probes skipped")
+    _require_dev(code, code_flip, labels, lin_counts, clu_counts)
+    B, K, h, w = code.shape
+    if labels.dtype != torch.int64 or labels.dim() != 3 or labels.shape[0] != B:
+        raise ValueError("labels: expected int64 [%d, H, W], got %s %s" % (B, labels.dtype, tuple(labels.shape)))
+    if code_flip is not None and tuple(code_flip.shape) != tuple(code.shape):
+        raise ValueError("code_flip %s does not match code %s" % (tuple(code_flip.shape), tuple(code.shape)))
+    H, W = int(labels.shape[1]), int(labels.shape[2])
+    n_classes = int((lin_counts if lin_counts is not None else clu_counts).shape[1])
+    lw = lb = ce = None
+    n_lin = n_clu = 0
+    if lin_counts is not None:
+        _require_dev(lin_w, lin_b)
+        lw, lb = _dense(lin_w, torch.float32), _dense(lin_b, torch.float32)
+        n_lin = int(lw.shape[0])
+        if tuple(lw.shape) != (n_lin, K) or tuple(lb.shape) != (n_lin,):
+            raise ValueError("linear probe weights %s / %s do not match K = %d" % (tuple(lw.shape), tuple(lb.shape), K))
+        _counts_ok(lin_counts, n_lin, n_classes, "lin_counts")
+    if clu_counts is not None:
+        _require_dev(centroids)
+        ce = _dense(centroids, torch.float32)
+        n_clu = int(ce.shape[0])
+        if tuple(ce.shape) != (n_clu, K):
+            raise ValueError("centroids %s do not match K = %d" % (tuple(ce.shape), K))
+        _counts_ok(clu_counts, n_clu, n_classes, "clu_counts")
+    labels = labels.contiguous()
+    desc = probe_confusion_desc(B, K, h, w, H, W, n_lin, n_clu, lin_counts is not None, clu_counts is not None, alpha, n_classes)
+    with _on_device(code.device):
+        _check(probe_confusion_raw(desc, _map(code), _map(code_flip) if code_flip is not None else None, lw, lb, ce, labels,
+                                   lin_counts, clu_counts, _stream()))
+
+
+def confusion_raw(desc, pred, labels, counts, stream=None):
+    """stego_confusion with raw addresses or tensors (tests: the error codes) -> the return code, unchecked."""
+    return int(load().stego_confusion(byref(desc) if desc is not None else None, _addr(pred), _addr(labels), _addr(counts),
+                                      stream if stream is not None else None))
+
+
+def confusion(pred, labels, counts, kind):
+    """stego_confusion: `pred` is int64 [B, H, W] label maps (kind "labels") or float32 [B, n, H, W] scores (kind "scores": the
+    prediction is the first maximum over n), labels int64 [B, H, W]; counts int64 [n, n_classes] is added onto in place.  Nothing is
+    returned and nothing synchronises."""
+    if kind not in CONF_KINDS:
+        raise ValueError("confusion: kinds are %s, got %r" % (sorted(CONF_KINDS), kind))
+    _require_dev(pred, labels, counts)
+    if counts.dtype != torch.int64 or counts.dim() != 2 or not counts.is_contiguous():
+        raise ValueError("counts: expected a contiguous int64 [n, n_classes] tensor, got %s %s" % (counts.dtype, tuple(counts.shape)))
+    n, n_classes = int(counts.shape[0]), int(counts.shape[1])
+    if labels.dtype != torch.int64 or labels.dim() != 3:
+        raise ValueError("labels: expected int64 [B, H, W], got %s %s" % (labels.dtype, tuple(labels.shape)))
+    B, H, W = labels.shape
+    if kind == "scores":
+        if pred.dtype != torch.float32 or tuple(pred.shape) != (B, n, H, W):
+            raise ValueError("scores: expected float32 %s, got %s %s" % ((B, n, H, W), pred.dtype, tuple(pred.shape)))
+    elif pred.dtype != torch.int64 or tuple(pred.shape) != (B, H, W):
+        raise ValueError("label maps: expected int64 %s, got %s %s" % ((B, H, W), pred.dtype, tuple(pred.shape)))
+    pred, labels = pred.contiguous(), labels.contiguous()
+    desc = confusion_desc(B, n, H, W, n_classes, CONF_KINDS[kind])
+    with _on_device(labels.device):
+        _check(confusion_raw(desc, pred, labels, counts, _stream()))
 
 
 # ---- fused training tail of the two probes (include/stego_probe_train.h; stego_amd.probe_train wraps it for the trainer)

@@ -15,6 +15,7 @@
 #include "../../include/stego_heat.h"
 #include "../../include/stego_crf_loss.h"
 #include "../../include/stego_aug.h"
+#include "../../include/stego_confusion.h"
 #include "corr_wide.h"
 
 namespace stego {
@@ -395,6 +396,10 @@ const char* stego_error_string(int code)
         case STEGO_ERR_AUG_PARAM: return "augment: a record of the parameter table is invalid (flip, crop, order, factors, gray or blur_sigma; include/stego_aug.h)";
         case STEGO_ERR_AUGALIGN_DIM: return "aug alignment: K outside [1, 128] (include/stego_aug.h)";
         case STEGO_ERR_AUGALIGN_SIZE: return "aug alignment: B outside [1, 65535], a side of code or code_aug outside [1, 256], or a side of coord outside [1, 2048]";
+        case STEGO_ERR_CONF_DIM: return "confusion: K outside [1, 128], or an active probe's labels, n or n_classes outside [1, 64] (include/stego_confusion.h)";
+        case STEGO_ERR_CONF_SIZE: return "confusion: B, a code side or a label side out of range (probe confusion: B <= 65535, code <= 65535, labels <= 2048; otherwise B * H * W < 2^40)";
+        case STEGO_ERR_CONF_PROBES: return "confusion: lin_on or clu_on neither 0 nor 1, or both probes skipped";
+        case STEGO_ERR_CONF_KIND: return "confusion: pred_kind is neither STEGO_CONF_LABELS nor STEGO_CONF_SCORES";
         case STEGO_ERR_CRF_RANGE: return "dense CRF: a lattice coordinate would leave the packed key (image too large for its standard deviations)";
         default: return code >= STEGO_ERR_HIP ? "HIP runtime error (code - 1000 = hipError_t)" : "unknown error";
     }

@@ -34,13 +34,36 @@ def _fused_preds(model, img, code1, code2, size, run_crf):
     return dense_crf_batch(bgr, linear_probs).argmax(1), dense_crf_batch(bgr, cluster_probs).argmax(1)
 
 
-def evaluate(model, loader, run_crf=True, device=None, fused_head=False):
+def _native_update(model, img, code1, code2, label, run_crf):
+    """One batch into the model's DeviceUnsupervisedMetrics with no label map, no log-probability tensor and no host sync: without
+    CRF one fused call from the low-resolution codes to both confusion matrices; with CRF the fused head's probabilities go through
+    the dense CRF as in _fused_preds and the kernel takes the argmax of its output while it counts."""
+    from .metrics import probe_confusion
+    if not run_crf:
+        probe_confusion(model, code1, code2, label, model.test_linear_metrics, model.test_cluster_metrics)
+        return
+    from .segment import probe_head
+    linear_probs, cluster_probs = probe_head(model, code1, code2, img.shape[-2:], linear="probs", cluster="probs")
+    bgr = image_to_bgr_u8(img)
+    model.test_linear_metrics.update_scores(dense_crf_batch(bgr, linear_probs), label)
+    model.test_cluster_metrics.update_scores(dense_crf_batch(bgr, cluster_probs), label)
+
+
+def evaluate(model, loader, run_crf=True, device=None, fused_head=False, native_metrics=False):
     """eval_segmentation.py:118-161 over `loader` (batches with "img" / "label", or (img, label, ...) tuples) -> the metrics dict of
     model.test_linear_metrics and model.test_cluster_metrics (reset first, then updated batch by batch, then computed).
     fused_head: the flip average, resize and both probes in one launch (stego_amd.segment.probe_head), which writes the CRF's
-    probabilities directly (run_crf) or the log-probabilities the argmax takes, instead of the torch chain."""
+    probabilities directly (run_crf) or the log-probabilities the argmax takes, instead of the torch chain.
+    native_metrics: the confusion matrices are counted on the device (stego_amd.metrics) and read once, in compute(); implies the
+    fused head.  The model's test metrics become DeviceUnsupervisedMetrics for it when they are not already."""
     device = device or next(model.parameters()).device
     model.eval()
+    if native_metrics:
+        from .metrics import DeviceUnsupervisedMetrics
+        for name in ("test_linear_metrics", "test_cluster_metrics"):
+            m = getattr(model, name)
+            if not isinstance(m, DeviceUnsupervisedMetrics):
+                setattr(model, name, DeviceUnsupervisedMetrics(m.prefix, m.n_classes, m.extra_clusters, m.compute_hungarian))
     model.test_linear_metrics.reset()
     model.test_cluster_metrics.reset()
     with torch.no_grad():
@@ -49,6 +72,9 @@ def evaluate(model, loader, run_crf=True, device=None, fused_head=False):
             img, label = img.to(device), label.to(device)
             _, code1 = model.net(img)
             _, code2 = model.net(img.flip(dims=[3]))
+            if native_metrics:
+                _native_update(model, img, code1, code2, label, run_crf)
+                continue
             if fused_head:
                 linear_preds, cluster_preds = _fused_preds(model, img, code1, code2, label.shape[-2:], run_crf)
             else:
@@ -88,7 +114,8 @@ def my_app(cfg):
     for model_path in cfg.model_paths:
         model = LitUnsupervisedSegmenter.load_from_checkpoint(model_path)
         model.eval().to(dev)
-        metrics = evaluate(model, make_loader(cfg, model), run_crf=cfg.run_crf, device=dev, fused_head=getattr(cfg, "fused_head", False))
+        metrics = evaluate(model, make_loader(cfg, model), run_crf=cfg.run_crf, device=dev, fused_head=getattr(cfg, "fused_head", False),
+                           native_metrics=getattr(cfg, "native_metrics", False))
         print("")
         print(model_path)
         print({k: float(v) for k, v in metrics.items()})

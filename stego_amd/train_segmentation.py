@@ -26,6 +26,7 @@ from .augment import Augmenter, aug_alignment_loss, needs_torchvision
 from .featurizers import ClusterLookup, ContrastiveCRFLoss, DinoFeaturizer, FeaturePyramidNet
 from .modules import ContrastiveCorrelationLoss, norm, sample
 from .probe_train import probe_losses, torch_probe_losses
+from .metrics import DeviceUnsupervisedMetrics, probe_confusion
 from .utils import UnsupervisedMetrics, one_hot_feats, prep_args, resize
 
 
@@ -79,10 +80,12 @@ class LitUnsupervisedSegmenter(nn.Module):
         self.cluster_probe = ClusterLookup(dim, n_classes + cfg.extra_clusters)
         self.linear_probe = nn.Conv2d(dim, n_classes, (1, 1))
         self.decoder = nn.Conv2d(dim, self.net.n_feats, (1, 1))
-        self.cluster_metrics = UnsupervisedMetrics("test/cluster/", n_classes, cfg.extra_clusters, True)
-        self.linear_metrics = UnsupervisedMetrics("test/linear/", n_classes, 0, False)
-        self.test_cluster_metrics = UnsupervisedMetrics("final/cluster/", n_classes, cfg.extra_clusters, True)
-        self.test_linear_metrics = UnsupervisedMetrics("final/linear/", n_classes, 0, False)
+        # cfg.native_metrics: the confusion matrices stay on the device and validation_step scores with one fused call (stego_amd.metrics)
+        Metrics = DeviceUnsupervisedMetrics if getattr(cfg, "native_metrics", False) else UnsupervisedMetrics
+        self.cluster_metrics = Metrics("test/cluster/", n_classes, cfg.extra_clusters, True)
+        self.linear_metrics = Metrics("test/linear/", n_classes, 0, False)
+        self.test_cluster_metrics = Metrics("final/cluster/", n_classes, cfg.extra_clusters, True)
+        self.test_linear_metrics = Metrics("final/linear/", n_classes, 0, False)
         self.linear_probe_loss_fn = nn.CrossEntropyLoss()
         self.crf_loss_fn = ContrastiveCRFLoss(cfg.crf_samples, cfg.alpha, cfg.beta, cfg.gamma, cfg.w1, cfg.w2, cfg.shift)
         self.contrastive_corr_loss_fn = ContrastiveCorrelationLoss(cfg)
@@ -315,13 +318,21 @@ class LitUnsupervisedSegmenter(nn.Module):
         self.net.eval()
         with torch.no_grad():
             _, code = self.net(img)
+            n = self.cfg.n_images
+            if getattr(self.cfg, "native_metrics", False):
+                # both confusion matrices from the low-resolution code in one launch, nothing per pixel and no host sync; the label
+                # maps of the n images the caller plots come from the fused head
+                from .segment import probe_head
+                probe_confusion(self, code, None, label, self.linear_metrics, self.cluster_metrics)
+                linear_preds, cluster_preds = probe_head(self, code[:n], None, label.shape[-2:], linear="argmax", cluster="argmax")
+                return {'img': img[:n].detach().cpu(), 'linear_preds': linear_preds.cpu(), "cluster_preds": cluster_preds.cpu(),
+                        "label": label[:n].detach().cpu()}
             code = F.interpolate(code, label.shape[-2:], mode='bilinear', align_corners=False)
             linear_preds = self.linear_probe(code).argmax(1)
             self.linear_metrics.update(linear_preds, label)
             _, cluster_preds = self.cluster_probe(code, None)
             cluster_preds = cluster_preds.argmax(1)
             self.cluster_metrics.update(cluster_preds, label)
-            n = self.cfg.n_images
             return {'img': img[:n].detach().cpu(), 'linear_preds': linear_preds[:n].detach().cpu(),
                     "cluster_preds": cluster_preds[:n].detach().cpu(), "label": label[:n].detach().cpu()}
 

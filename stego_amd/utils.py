@@ -58,13 +58,17 @@ class UnsupervisedMetrics:
             self.stats += hist.reshape(self.n_classes, rows).t().cpu()
 
     def compute(self):
-        from scipy.optimize import linear_sum_assignment
         stats = self.stats.clone()
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             buf = stats.cuda() if dist.get_backend() == "nccl" else stats
             dist.all_reduce(buf)
             stats = buf.cpu()
+        return self._scores(stats)
+
+    def _scores(self, stats):
+        """mIoU and accuracy of one (already cross-rank summed) host matrix."""
+        from scipy.optimize import linear_sum_assignment
         if self.compute_hungarian:
             self.assignments = linear_sum_assignment(stats.numpy(), maximize=True)
             if self.extra_clusters == 0:
