@@ -161,6 +161,27 @@ AUG_BRIGHTNESS, AUG_CONTRAST, AUG_SATURATION, AUG_HUE, AUG_NONE = 0, 1, 2, 3, 4
 AUG_MAX_SIDE, AUG_MIN_RES, AUG_LAUNCHES, AUGALIGN_MAX_K, AUGALIGN_MAX_SIDE, AUGALIGN_LAUNCHES = 2048, 3, 2, 128, 256, 2
 
 
+class StegoAdamSegment(Structure):
+    """include/stego_optim.h: one record of the segment table (40 bytes)"""
+    _fields_ = [("param", c_void_p), ("count", c_int64), ("grad_offset", c_int64), ("state_offset", c_int64), ("group", c_int32),
+                ("reserved", c_int32)]
+
+
+class StegoAdamGroup(Structure):
+    """include/stego_optim.h"""
+    _fields_ = [(n, ctypes.c_double) for n in ("lr", "beta1", "beta2", "eps")] + [("active", c_int32), ("reserved", c_int32)]
+
+
+OPTIM_ERR_COUNT, OPTIM_ERR_SEGMENT, OPTIM_ERR_PARAM, OPTIM_ERR_FLAGS = 110, 111, 112, 113
+ADAM_MAX_SEGMENTS, ADAM_MAX_GROUPS, ADAM_MAX_ELEMS, ADAM_CHUNK, ADAM_MAX_GRID = 256, 8, 1 << 31, 1024, 2048
+
+
+class StegoAdamDesc(Structure):
+    """include/stego_optim.h"""
+    _fields_ = [(n, c_int32) for n in ("n_segments", "n_groups", "zero_grads", "reserved")] + \
+        [("grad_elems", c_int64), ("state_elems", c_int64), ("groups", StegoAdamGroup * ADAM_MAX_GROUPS)]
+
+
 _H = POINTER(StegoHeadDesc)
 _D = POINTER(StegoCorrDesc)
 _M = POINTER(StegoMap)
@@ -185,6 +206,8 @@ SIGNATURES = {
     "stego_probe_confusion": (c_int32, [POINTER(StegoProbeConfusionDesc), _M, _M] + [_P] * 6 + [_P]),
     "stego_probe_confusion_plan": (c_size_t, [POINTER(StegoProbeConfusionDesc), POINTER(c_int32), POINTER(c_int32)]),
     "stego_confusion": (c_int32, [POINTER(StegoConfusionDesc), _P, _P, _P, _P]),
+    "stego_adam_step": (c_int32, [POINTER(StegoAdamDesc), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "stego_adam_plan": (c_int32, [POINTER(StegoAdamDesc), _P, POINTER(c_int32), POINTER(c_int32), POINTER(c_int64)]),
     "stego_pr_accumulate": (c_int32, [POINTER(StegoPrDesc), _M, _M] + [_P] * 6 + [_P]),
     "stego_pr_plan": (c_size_t, [POINTER(StegoPrDesc), POINTER(c_int32), POINTER(c_int32)]),
     "stego_probe_train_workspace_bytes": (c_size_t, [POINTER(StegoProbeTrainDesc)]),
@@ -1232,6 +1255,52 @@ def confusion(pred, labels, counts, kind):
     desc = confusion_desc(B, n, H, W, n_classes, CONF_KINDS[kind])
     with _on_device(labels.device):
         _check(confusion_raw(desc, pred, labels, counts, _stream()))
+
+
+# ---- fused Adam step (include/stego_optim.h; stego_amd.optim.FusedAdam wraps it for the trainer)
+def adam_segments(records):
+    """The host copy of the segment table: (param address, count, grad_offset, state_offset, group) per record -> a ctypes array."""
+    table = (StegoAdamSegment * max(len(records), 1))()
+    for r, (addr, count, grad_offset, state_offset, group) in zip(table, records):
+        r.param, r.count, r.grad_offset, r.state_offset, r.group = addr, int(count), int(grad_offset), int(state_offset), int(group)
+    return table
+
+
+def adam_desc(n_segments, groups, zero_grads, grad_elems, state_elems, n_groups=None):
+    """`groups`: (lr, beta1, beta2, eps[, active]) per group, at most ADAM_MAX_GROUPS of them."""
+    d = StegoAdamDesc(int(n_segments), len(groups) if n_groups is None else int(n_groups), int(zero_grads), 0, int(grad_elems),
+                      int(state_elems))
+    for g, vals in zip(d.groups, groups):
+        g.lr, g.beta1, g.beta2, g.eps = (float(x) for x in vals[:4])
+        g.active = int(vals[4]) if len(vals) > 4 else 1
+    return d
+
+
+def adam_plan(desc, segments_host):
+    """stego_adam_plan (host only) -> (return code, grid, chunk, n_chunks); the last three are 0 when the code is not 0."""
+    grid, chunk, n = c_int32(0), c_int32(0), c_int64(0)
+    rc = load().stego_adam_plan(byref(desc) if desc is not None else None,
+                                ctypes.addressof(segments_host) if segments_host is not None else None, byref(grid), byref(chunk),
+                                byref(n))
+    return int(rc), grid.value, chunk.value, n.value
+
+
+def adam_step_raw(desc, segments_host, segments, grads, exp_avg, exp_avg_sq, steps, ticket, stream=None):
+    """stego_adam_step with every argument given: `segments_host` a ctypes array (or None), the rest raw addresses or tensors (tests:
+    the error codes) -> the return code, unchecked."""
+    return int(load().stego_adam_step(byref(desc) if desc is not None else None,
+                                      ctypes.addressof(segments_host) if segments_host is not None else None, _addr(segments),
+                                      _addr(grads), _addr(exp_avg), _addr(exp_avg_sq), _addr(steps), _addr(ticket),
+                                      stream if stream is not None else None))
+
+
+def adam_step(desc, segments_host, segments, grads, exp_avg, exp_avg_sq, steps, ticket):
+    """stego_adam_step on torch's current stream: `segments` is the device copy of `segments_host` (a uint8 tensor), grads / exp_avg /
+    exp_avg_sq flat float32 tensors, steps int32 [n_groups], ticket int32 [1] (zero before the first call).  One launch; nothing is
+    returned and nothing synchronises."""
+    _require_dev(segments, grads, exp_avg, exp_avg_sq, steps, ticket)
+    with _on_device(grads.device):
+        _check(adam_step_raw(desc, segments_host, segments, grads, exp_avg, exp_avg_sq, steps, ticket, _stream()))
 
 
 # ---- fused training tail of the two probes (include/stego_probe_train.h; stego_amd.probe_train wraps it for the trainer)

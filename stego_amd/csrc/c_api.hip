@@ -16,6 +16,7 @@
 #include "../../include/stego_crf_loss.h"
 #include "../../include/stego_aug.h"
 #include "../../include/stego_confusion.h"
+#include "../../include/stego_optim.h"
 #include "corr_wide.h"
 
 namespace stego {
@@ -400,6 +401,10 @@ const char* stego_error_string(int code)
         case STEGO_ERR_CONF_SIZE: return "confusion: B, a code side or a label side out of range (probe confusion: B <= 65535, code <= 65535, labels <= 2048; otherwise B * H * W < 2^40)";
         case STEGO_ERR_CONF_PROBES: return "confusion: lin_on or clu_on neither 0 nor 1, or both probes skipped";
         case STEGO_ERR_CONF_KIND: return "confusion: pred_kind is neither STEGO_CONF_LABELS nor STEGO_CONF_SCORES";
+        case STEGO_ERR_OPTIM_COUNT: return "fused Adam: n_segments outside [1, 256], n_groups outside [1, 8], or 2^31 elements or more in all (include/stego_optim.h)";
+        case STEGO_ERR_OPTIM_SEGMENT: return "fused Adam: a segment with count < 1, a group index out of range, or a gradient or state slice outside its buffer";
+        case STEGO_ERR_OPTIM_PARAM: return "fused Adam: a beta outside [0, 1), or lr or eps negative or not finite";
+        case STEGO_ERR_OPTIM_FLAGS: return "fused Adam: zero_grads or a group's active flag neither 0 nor 1, or no active group";
         case STEGO_ERR_CRF_RANGE: return "dense CRF: a lattice coordinate would leave the packed key (image too large for its standard deviations)";
         default: return code >= STEGO_ERR_HIP ? "HIP runtime error (code - 1000 = hipError_t)" : "unknown error";
     }

@@ -130,6 +130,7 @@ class LitUnsupervisedSegmenter(nn.Module):
         self.global_step = 0
         self.logged = {}
         self._optims = None
+        self._fused = None               # cfg.native_optim: the FusedAdam behind the three optimizers (stego_amd.optim)
         self._reducer = None
         self._augmenter = None
 
@@ -175,16 +176,30 @@ class LitUnsupervisedSegmenter(nn.Module):
     def log(self, name, value, **_):
         self.logged[name] = value.detach() if torch.is_tensor(value) else value
 
-    def configure_optimizers(self):
+    def optimizer_groups(self):
+        """The three parameter lists of train_segmentation.py:117-119 with their learning rates: net (+ decoder), linear probe,
+        cluster probe."""
         main_params = list(self.net.parameters())
         if self.cfg.rec_weight > 0:
             main_params.extend(self.decoder.parameters())
-        net_optim = torch.optim.Adam(main_params, lr=self.cfg.lr)
-        linear_probe_optim = torch.optim.Adam(list(self.linear_probe.parameters()), lr=5e-3)
-        cluster_probe_optim = torch.optim.Adam(list(self.cluster_probe.parameters()), lr=5e-3)
+        return [{"params": main_params, "lr": self.cfg.lr}, {"params": list(self.linear_probe.parameters()), "lr": 5e-3},
+                {"params": list(self.cluster_probe.parameters()), "lr": 5e-3}]
+
+    def configure_optimizers(self):
+        net_optim, linear_probe_optim, cluster_probe_optim = (torch.optim.Adam(g["params"], lr=g["lr"]) for g in self.optimizer_groups())
         return net_optim, linear_probe_optim, cluster_probe_optim
 
     def optimizers(self):
+        """The three optimizers (net, linear probe, cluster probe).  cfg.native_optim on a HIP device: the three facades of one
+        FusedAdam (stego_amd.optim) - built here, or built from the torch optimizers a CPU model has used so far (a checkpoint
+        is loaded before the model moves to its device), whose state they take over.  On the CPU the flag changes nothing."""
+        if getattr(self.cfg, "native_optim", False) and self._fused is None and self.linear_probe.weight.is_cuda:
+            from .optim import FusedAdam
+            fused = FusedAdam(self.optimizer_groups(), reducer=self._reducer,
+                              zero_grads=getattr(self.cfg, "native_optim_zero", True))
+            if self._optims is not None:
+                fused.load_state_dict([o.state_dict() for o in self._optims])
+            self._fused, self._optims = fused, list(fused.groups)
         if self._optims is None:
             self._optims = list(self.configure_optimizers())
         return self._optims
@@ -192,6 +207,8 @@ class LitUnsupervisedSegmenter(nn.Module):
     def setup_distributed(self):
         """Flat gradient bucket over every trainable parameter + startup broadcast (what DDP does on wrap)."""
         self._reducer = ddp.FlatGradReducer([p for p in self.parameters() if p.requires_grad])
+        if self._fused is not None:
+            self._fused.use_bucket(self._reducer)
         self._reducer.broadcast_params(0)
         return self._reducer
 
@@ -205,6 +222,8 @@ class LitUnsupervisedSegmenter(nn.Module):
         """loss.backward() + the DDP gradient exchange (Lightning's manual_backward under accelerator='ddp',
         train_segmentation.py:227): ONE asynchronous averaged all-reduce of the flat bucket; wait_gradients() joins it."""
         loss.backward()
+        if self._fused is not None and self._reducer is None:
+            self._fused.bucket.reattach()       # the fused step reads the bucket: a replaced .grad is copied into its slot
         if self._reducer is not None:
             self._reducer.reattach()
             # (force_collective: run the collective on a process group of ONE - the single-GPU dress rehearsal of the N > 1 path)
@@ -217,7 +236,15 @@ class LitUnsupervisedSegmenter(nn.Module):
 
     def training_step(self, batch, batch_idx):
         net_optim, linear_probe_optim, cluster_probe_optim = self.optimizers()
-        if self._reducer is not None:
+        fused = self._fused
+        if fused is not None:
+            # cfg.native_optim: the previous fused step left the bucket zeroed; the first step, or native_optim_zero=False: zero it here
+            fused.zero_grads = bool(getattr(self.cfg, "native_optim_zero", True))
+            if fused.zero_grads and fused.bucket_zeroed:
+                fused.zero_uncovered()          # trainable tensors of a shared bucket that no optimizer owns; none without data parallelism
+            else:
+                fused.zero_grad()
+        elif self._reducer is not None:
             self._reducer.zero_grad()
         else:
             net_optim.zero_grad(); linear_probe_optim.zero_grad(); cluster_probe_optim.zero_grad()
@@ -300,16 +327,23 @@ class LitUnsupervisedSegmenter(nn.Module):
 
         self.manual_backward(loss)
         self.wait_gradients()
-        net_optim.step()
-        cluster_probe_optim.step()
-        linear_probe_optim.step()
+        if fused is not None:
+            fused.step()                        # all three groups in one launch (include/stego_optim.h)
+        else:
+            net_optim.step()
+            cluster_probe_optim.step()
+            linear_probe_optim.step()
 
         if cfg.reset_probe_steps is not None and self.global_step == cfg.reset_probe_steps:
             print("RESETTING PROBES")
             self.linear_probe.reset_parameters()
             self.cluster_probe.reset_parameters()
-            self._optims[1] = torch.optim.Adam(list(self.linear_probe.parameters()), lr=5e-3)
-            self._optims[2] = torch.optim.Adam(list(self.cluster_probe.parameters()), lr=5e-3)
+            if fused is not None:
+                fused.reset_group(1)
+                fused.reset_group(2)
+            else:
+                self._optims[1] = torch.optim.Adam(list(self.linear_probe.parameters()), lr=5e-3)
+                self._optims[2] = torch.optim.Adam(list(self.cluster_probe.parameters()), lr=5e-3)
         self.global_step += 1
         return loss
 
