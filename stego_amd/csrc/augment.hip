@@ -429,8 +429,8 @@ __global__ __launch_bounds__(TPB) void align_finish(AlignP p, int cell_blocks, i
     }
 }
 
-inline int hip_rc(hipError_t e) { return e == hipSuccess ? STEGO_OK : STEGO_ERR_HIP + (int)e; }
-inline bool aligned(const void* ptr, size_t a) { return (reinterpret_cast<uintptr_t>(ptr) % a) == 0; }
+using stego::aligned;
+using stego::hip_rc;
 inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 int check_aug(const StegoAugDesc* d)

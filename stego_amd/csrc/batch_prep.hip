@@ -13,6 +13,7 @@
 #include <cstdint>
 
 #include "../../include/stego_data.h"
+#include "host_util.h"
 
 namespace {
 
@@ -108,9 +109,8 @@ __global__ __launch_bounds__(TPB) void batch_prep_kernel(PrepParams p)
     }
 }
 
-inline int hip_rc(hipError_t e) { return e == hipSuccess ? STEGO_OK : STEGO_ERR_HIP + (int)e; }
-
-inline bool aligned(const void* ptr, size_t a) { return (reinterpret_cast<uintptr_t>(ptr) % a) == 0; }
+using stego::aligned;
+using stego::hip_rc;
 
 int check_desc(const StegoDataDesc* d)
 {

@@ -145,8 +145,6 @@ Geometry geometry(const StegoCorrDesc* d, bool helper)
     return g;
 }
 
-int hip_rc(hipError_t e) { return e == hipSuccess ? STEGO_OK : STEGO_ERR_HIP + (int)e; }
-
 // feature_samples 12 .. 16: more points than one tile holds - the multi-launch path of corr_wide.hip behind the same entry points
 bool is_wide(const StegoCorrDesc* d) { return d->S * d->S > TP; }
 WideGeom wide_geom(const StegoCorrDesc* d) { return wide_geometry(d->B, d->C, d->K, d->H, d->W, d->S, d->n_neg); }

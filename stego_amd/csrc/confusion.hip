@@ -1,13 +1,10 @@
 // Device-side confusion matrices (include/stego_confusion.h): the fused probe head with the two matrices as its only output, and the
 // same counting for label maps and score planes made elsewhere.
 //
-// probe_confusion_kernel is probe_head.hip's kernel with another sink.  probe_head.hip is left as it is (two tests pin its four
-// kernels' registers and occupancy), so its phases are restated here and must stay in step with it:
-//   phase 1, the footprint load            mirrors probe_head.hip:106-116
-//   phase 2, the projections               mirrors probe_head.hip:119-140
-//   phase 3, taps, logits and the norm     mirrors probe_head.hip:150-162, 165-174, 178-202
-//   first_max, the label                   mirrors finish()'s ARGMAX branch, probe_head.hip:49-54, 64, 75-82
-// tests/test_confusion_gpu.py holds the two kernels' predictions equal bit for bit.
+// probe_confusion_kernel is probe_head.hip's kernel with another sink: both are built from the phases of probe_phases.h (footprint
+// load, projections, taps, logits, the first maximum), so the label counted here is the label the head's ARGMAX kind writes, by
+// construction; tests/test_confusion_gpu.py also holds the two equal bit for bit.  What is this kernel's own: the tile loop, the label
+// read, the ConfMaps copy in LDS and the counting.
 //
 // Grid: sized from the compute units, not from the pixels.  A workgroup of 256 threads walks the label tiles (column tiles, row tiles,
 // images; tile t, t + grid, ...) and keeps one uint32 histogram per active probe in LDS, [n, n_classes] as in global memory.  Per tile
@@ -24,11 +21,11 @@
 
 #include "../../include/stego_confusion.h"
 #include "host_util.h"
-#include "probe_common.h"
+#include "probe_phases.h"
 
 namespace {
 
-constexpr int TPB = 256;
+constexpr int TPB = PROBE_TPB;
 constexpr size_t LDS_BUDGET = 64 * 1024;
 constexpr int WGS_PER_CU = 4;
 // a workgroup's uint32 bins must not wrap before it flushes them: the host sizes the grid so that none counts more pixels than this
@@ -80,28 +77,6 @@ __device__ inline void flush(unsigned* hist, int bins, unsigned long long* count
     }
 }
 
-// finish()'s ARGMAX: the first maximum of the values LOG_PROBS would write; l[n, NMAX) are -inf and never win.
-template <int NMAX>
-__device__ inline int first_max(const float (&l)[NMAX])
-{
-    float m = l[0];
-#pragma unroll
-    for (int j = 1; j < NMAX; ++j) m = fmaxf(m, l[j]);
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < NMAX; ++j) s += expf(l[j] - m);
-    const float ls = logf(s);
-    int best = 0;
-    float bv = (l[0] - m) - ls;
-#pragma unroll
-    for (int j = 1; j < NMAX; ++j) {
-        const float v = (l[j] - m) - ls;
-        best = v > bv ? j : best;
-        bv = v > bv ? v : bv;
-    }
-    return best;
-}
-
 template <int NMAX>
 __global__ __launch_bounds__(TPB) void probe_confusion_kernel(ConfParams p)
 {
@@ -116,10 +91,7 @@ __global__ __launch_bounds__(TPB) void probe_confusion_kernel(ConfParams p)
     unsigned* const clu_hist = lin_hist + lin_bins;
 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (threadIdx.x < 2 * NMAX) {
-        const int j = threadIdx.x;
-        mask[j] = (j < NMAX ? j < p.n_lin : j - NMAX < p.n_clu) ? 0.f : -INFINITY;
-    }
+    init_mask<NMAX>(mask, p.n_lin, p.n_clu);
     for (int i = threadIdx.x; i < lin_bins + clu_bins; i += TPB) lin_hist[i] = 0;
     if (threadIdx.x == 0) *maps = p.maps;
 
@@ -141,49 +113,16 @@ __global__ __launch_bounds__(TPB) void probe_confusion_kernel(ConfParams p)
         const int Y1 = min(Y0 + p.TY, p.H), X1 = min(X0 + p.TX, p.W);
         __syncthreads();                                            // the tile before is done with cs / ps; the first: maps, mask, bins
         const float scale_h = maps->scale_h, scale_w = maps->scale_w;
-        int ya, yb, xa, xb, t0;
-        float tl;
-        src_index(Y0, scale_h, p.h, ya, t0, tl);
-        src_index(Y1 - 1, scale_h, p.h, t0, yb, tl);
-        src_index(X0, scale_w, p.w, xa, t0, tl);
-        src_index(X1 - 1, scale_w, p.w, t0, xb, tl);
-        const int nr = min(yb - ya + 1, p.max_nr), nc = min(xb - xa + 1, p.max_nc);
-        const int npx = nr * nc;
+        const Footprint f = tile_footprint(Y0, Y1, X0, X1, scale_h, scale_w, p.h, p.w, p.max_nr, p.max_nc);
 
-        // 1. the footprint's code, flip-averaged, channels K .. K4 zeroed
+        // phases 1 and 2 of the head (probe_phases.h): the footprint's code, then its projections onto both probes
         const StegoMap code = maps->code, flip = maps->flip;
-        for (int i = threadIdx.x; i < npx * p.K4; i += TPB) {
-            const int k = i % p.K4, px = i / p.K4;
-            const int y = ya + px / nc, x = xa + px % nc;
-            float v = 0.f;
-            if (k < p.K) {
-                v = load_code(code, b, k, y, x);
-                if (p.has_flip) v = (v + load_code(flip, b, k, y, p.w - 1 - x)) * 0.5f;
-            }
-            cs[px * p.KS + k] = v;
-        }
+        load_footprint(cs, code, flip, p.has_flip != 0, b, f, p.K, p.K4, p.KS, p.w);
+        __syncthreads();
+        project<NMAX>(ps, cs, p.lin_w, p.lin_b, p.cent, p.n_lin, p.n_clu, p.K, p.KS, NPS, f.npx, wave, lane);
         __syncthreads();
 
-        // 2. projections: label slot j of both probes (linear slots [0, NMAX), cluster slots [NMAX, 2 NMAX)), one wave per slot
-        for (int j = wave; j < 2 * NMAX; j += TPB / 64) {
-            const bool lin = j < NMAX;
-            const int jj = lin ? j : j - NMAX;
-            const bool live = lin ? jj < p.n_lin : jj < p.n_clu;
-            const float* row = live ? (lin ? p.lin_w : p.cent) + (size_t)jj * p.K : nullptr;
-            const float bias = live && lin ? p.lin_b[jj] : 0.f;
-            for (int px = lane; px < npx; px += 64) {
-                float acc = 0.f;
-                if (live) {
-                    const float* c = cs + px * p.KS;
-                    for (int k = 0; k < p.K; ++k) acc = fmaf(row[k], c[k], acc);
-                    acc += bias;
-                }
-                ps[px * NPS + j] = acc;
-            }
-        }
-        __syncthreads();
-
-        // 3. one label pixel per thread (TY * TX <= 256); a thread without one keeps key -1 and stays for the wave's count
+        // phase 3: one label pixel per thread (TY * TX <= 256); a thread without one keeps key -1 and stays for the wave's count
         const int i = threadIdx.x;
         const int Y = Y0 + i / p.TX, X = X0 + i % p.TX;
         const bool has = i < p.TY * p.TX && Y < Y1 && X < X1;
@@ -192,56 +131,16 @@ __global__ __launch_bounds__(TPB) void probe_confusion_kernel(ConfParams p)
         const bool counted = label >= 0 && label < p.n_classes;
         int lin_key = -1, clu_key = -1;
         if (counted) {
-            int y0, y1, x0, x1;
-            float h1, w1;
-            src_index(Y, scale_h, p.h, y0, y1, h1);
-            src_index(X, scale_w, p.w, x0, x1, w1);
-            const float h0 = 1.f - h1, w0 = 1.f - w1;
-            // (clamps: memory safety only - the footprint covers every tap, the host plan one row / column more)
-            const int r0 = max(min(y0 - ya, nr - 1), 0), r1 = max(min(y1 - ya, nr - 1), 0);
-            const int c0 = max(min(x0 - xa, nc - 1), 0), c1 = max(min(x1 - xa, nc - 1), 0);
-            const int q00 = r0 * nc + c0, q01 = r0 * nc + c1, q10 = r1 * nc + c0, q11 = r1 * nc + c1;
-
+            const Taps t = pixel_taps(Y, X, scale_h, scale_w, p.h, p.w, f);
             if (p.n_lin) {
                 float l[NMAX];
-#pragma unroll
-                for (int g = 0; g < NMAX / 4; ++g) {
-                    const float4 a = ps4[q00 * NPS4 + g], bq = ps4[q01 * NPS4 + g], c = ps4[q10 * NPS4 + g], d = ps4[q11 * NPS4 + g];
-                    const float4 mk = mask4[g];
-                    l[4 * g + 0] = (h0 * (w0 * a.x + w1 * bq.x) + h1 * (w0 * c.x + w1 * d.x)) + mk.x;
-                    l[4 * g + 1] = (h0 * (w0 * a.y + w1 * bq.y) + h1 * (w0 * c.y + w1 * d.y)) + mk.y;
-                    l[4 * g + 2] = (h0 * (w0 * a.z + w1 * bq.z) + h1 * (w0 * c.z + w1 * d.z)) + mk.z;
-                    l[4 * g + 3] = (h0 * (w0 * a.w + w1 * bq.w) + h1 * (w0 * c.w + w1 * d.w)) + mk.w;
-                }
+                linear_logits<NMAX>(l, ps4, mask4, NPS4, t);
                 lin_key = first_max<NMAX>(l) * p.n_classes + (int)label;
             }
             if (p.n_clu) {
-                // F.normalize's denominator: the norm of the interpolated code, clamped at 1e-12
-                float4 n4 = make_float4(0.f, 0.f, 0.f, 0.f);
-                for (int k4 = 0; k4 < (p.K4 >> 2); ++k4) {
-                    const float4 a = cs4[q00 * KS4 + k4], bq = cs4[q01 * KS4 + k4], c = cs4[q10 * KS4 + k4], d = cs4[q11 * KS4 + k4];
-                    const float vx = h0 * (w0 * a.x + w1 * bq.x) + h1 * (w0 * c.x + w1 * d.x);
-                    const float vy = h0 * (w0 * a.y + w1 * bq.y) + h1 * (w0 * c.y + w1 * d.y);
-                    const float vz = h0 * (w0 * a.z + w1 * bq.z) + h1 * (w0 * c.z + w1 * d.z);
-                    const float vw = h0 * (w0 * a.w + w1 * bq.w) + h1 * (w0 * c.w + w1 * d.w);
-                    n4.x = fmaf(vx, vx, n4.x);
-                    n4.y = fmaf(vy, vy, n4.y);
-                    n4.z = fmaf(vz, vz, n4.z);
-                    n4.w = fmaf(vw, vw, n4.w);
-                }
-                const float den = fmaxf(sqrtf((n4.x + n4.y) + (n4.z + n4.w)), 1e-12f);
-                const float alpha = maps->alpha;
+                const float den = code_norm(cs4, KS4, p.K4, t);
                 float l[NMAX];
-#pragma unroll
-                for (int g = 0; g < NMAX / 4; ++g) {
-                    const int o = NMAX / 4 + g;
-                    const float4 a = ps4[q00 * NPS4 + o], bq = ps4[q01 * NPS4 + o], c = ps4[q10 * NPS4 + o], d = ps4[q11 * NPS4 + o];
-                    const float4 mk = mask4[o];
-                    l[4 * g + 0] = (h0 * (w0 * a.x + w1 * bq.x) + h1 * (w0 * c.x + w1 * d.x)) / den * alpha + mk.x;
-                    l[4 * g + 1] = (h0 * (w0 * a.y + w1 * bq.y) + h1 * (w0 * c.y + w1 * d.y)) / den * alpha + mk.y;
-                    l[4 * g + 2] = (h0 * (w0 * a.z + w1 * bq.z) + h1 * (w0 * c.z + w1 * d.z)) / den * alpha + mk.z;
-                    l[4 * g + 3] = (h0 * (w0 * a.w + w1 * bq.w) + h1 * (w0 * c.w + w1 * d.w)) / den * alpha + mk.w;
-                }
+                cluster_logits<NMAX>(l, ps4, mask4, NPS4, t, den, maps->alpha);
                 clu_key = first_max<NMAX>(l) * p.n_classes + (int)label;
             }
         }
@@ -301,9 +200,8 @@ __global__ __launch_bounds__(TPB) void confusion_count_kernel(CountParams p)
     flush(hist, bins, p.counts);
 }
 
-inline int hip_rc(hipError_t e) { return e == hipSuccess ? STEGO_OK : STEGO_ERR_HIP + (int)e; }
-
-inline bool aligned(const void* ptr, size_t a) { return (reinterpret_cast<uintptr_t>(ptr) % a) == 0; }
+using stego::aligned;
+using stego::hip_rc;
 
 int check_desc(const StegoProbeConfusionDesc* d)
 {
@@ -321,39 +219,13 @@ int check_desc(const StegoProbeConfusionDesc* d)
 
 static_assert(sizeof(ConfMaps) <= MAPS_FLOATS * sizeof(float), "ConfMaps outgrew its LDS slot");
 
-struct Plan {
-    int TY, TX, max_nr, max_nc, K4, KS, NMAX, NPS;
-    float scale_h, scale_w;
-    size_t lds;
-};
-
-// probe_head.hip's plan() with the histograms in the LDS figure: the tile shrinks until footprint and bins fit the budget together.
-Plan plan(const StegoProbeConfusionDesc* d)
+// The tile shrinks until footprint and histograms fit the budget together.
+TilePlan plan(const StegoProbeConfusionDesc* d)
 {
-    Plan pl{};
-    pl.scale_h = (float)d->h / (float)d->H;
-    pl.scale_w = (float)d->w / (float)d->W;
-    pl.K4 = round4(d->K);
-    pl.KS = pl.K4 + 4;
     const int n_lin = d->lin_on ? d->n_lin : 0, n_clu = d->clu_on ? d->n_clu : 0;
     const int n = std::max(n_lin, n_clu);
-    pl.NMAX = n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64;
-    pl.NPS = 2 * pl.NMAX + 4;
     const size_t hist = (size_t)(n_lin + n_clu) * d->n_classes * sizeof(unsigned);
-    pl.TX = d->W < 64 ? d->W : 64;
-    pl.TY = TPB / pl.TX;
-    pl.TY = pl.TY < d->H ? pl.TY : d->H;
-    for (;;) {
-        pl.max_nr = max_span(d->H, d->h, pl.scale_h, pl.TY);
-        pl.max_nc = max_span(d->W, d->w, pl.scale_w, pl.TX);
-        pl.lds = ((size_t)pl.max_nr * pl.max_nc * (pl.KS + pl.NPS) + 2 * pl.NMAX + MAPS_FLOATS) * sizeof(float) + hist;
-        if (pl.lds <= LDS_BUDGET || (pl.TY == 1 && pl.TX == 1)) break;
-        if (pl.TY > 1)
-            pl.TY = (pl.TY + 1) / 2;
-        else
-            pl.TX = (pl.TX + 1) / 2;
-    }
-    return pl;
+    return plan_tile(d->K, d->h, d->w, d->H, d->W, n, (2 * label_slots(n) + MAPS_FLOATS) * sizeof(float) + hist, LDS_BUDGET);
 }
 
 }  // namespace
@@ -361,7 +233,7 @@ Plan plan(const StegoProbeConfusionDesc* d)
 extern "C" size_t stego_probe_confusion_plan(const StegoProbeConfusionDesc* desc, int32_t* tile_rows, int32_t* tile_cols)
 {
     if (check_desc(desc) != STEGO_OK) return 0;
-    const Plan pl = plan(desc);
+    const TilePlan pl = plan(desc);
     if (tile_rows) *tile_rows = pl.TY;
     if (tile_cols) *tile_cols = pl.TX;
     return pl.lds;
@@ -380,7 +252,7 @@ extern "C" int stego_probe_confusion(const StegoProbeConfusionDesc* desc, const 
     if (lin && (!aligned(lin_w, 4) || !aligned(lin_b, 4) || !aligned(lin_counts, 8))) return STEGO_ERR_ALIGN;
     if (clu && (!aligned(centroids, 4) || !aligned(clu_counts, 8))) return STEGO_ERR_ALIGN;
 
-    const Plan pl = plan(desc);
+    const TilePlan pl = plan(desc);
     if (pl.lds > LDS_BUDGET) return STEGO_ERR_UNSUPPORTED;          // (unreachable: a 1 x 1 tile's footprint and both histograms fit)
     ConfParams p{};
     p.maps.code = *code;

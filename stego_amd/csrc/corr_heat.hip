@@ -355,10 +355,6 @@ __global__ __launch_bounds__(NTHREADS) void heat_write_kernel(WriteParams p)
     }
 }
 
-inline int hip_rc(hipError_t e) { return e == hipSuccess ? STEGO_OK : STEGO_ERR_HIP + (int)e; }
-
-inline bool aligned(const void* ptr, size_t a) { return (reinterpret_cast<uintptr_t>(ptr) % a) == 0; }
-
 int check_desc(const StegoHeatDesc* d)
 {
     if (!d) return STEGO_ERR_NULL;

@@ -219,10 +219,6 @@ __global__ __launch_bounds__(NTHREADS) void corr_pr_kernel(PrParams p)
     }
 }
 
-inline int hip_rc(hipError_t e) { return e == hipSuccess ? STEGO_OK : STEGO_ERR_HIP + (int)e; }
-
-inline bool aligned(const void* ptr, size_t a) { return (reinterpret_cast<uintptr_t>(ptr) % a) == 0; }
-
 inline bool side_ok(int v) { return v >= 1 && v <= STEGO_PR_MAX_SIDE; }
 
 int check_desc(const StegoPrDesc* d)

@@ -354,9 +354,8 @@ __global__ __launch_bounds__(FIN_TPB) void crf_finish(CrfParams p, int cell_bloc
     }
 }
 
-inline int hip_rc(hipError_t e) { return e == hipSuccess ? STEGO_OK : STEGO_ERR_HIP + (int)e; }
-
-inline bool aligned(const void* ptr, size_t a) { return (reinterpret_cast<uintptr_t>(ptr) % a) == 0; }
+using stego::aligned;
+using stego::hip_rc;
 
 inline bool side_ok(int v) { return v >= 1 && v <= STEGO_CRFLOSS_MAX_SIDE; }
 

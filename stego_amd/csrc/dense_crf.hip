@@ -29,6 +29,7 @@
 #include <cstdint>
 
 #include "../../include/stego_crf.h"
+#include "host_util.h"
 
 namespace stego_crf {
 
@@ -626,7 +627,7 @@ int check(const StegoCrfDesc* d)
     return STEGO_OK;
 }
 
-inline int hip_rc(hipError_t e) { return e == hipSuccess ? STEGO_OK : STEGO_ERR_HIP + (int)e; }
+using stego::hip_rc;
 
 inline dim3 grid(size_t work_items, int per_block, int B)
 {

@@ -1,8 +1,19 @@
-// Host-side helpers shared by the launchers: per-device caches (thread-safe), environment knobs read once.
+// Host-side helpers shared by the launchers: a HIP error as a C-ABI return code, the pointer alignment test, per-device caches
+// (thread-safe), environment knobs read once.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/stego_corr.h"
+
 namespace stego {
+
+// what a launcher returns for the runtime's answer to its launch
+inline int hip_rc(hipError_t e) { return e == hipSuccess ? STEGO_OK : STEGO_ERR_HIP + (int)e; }
+
+inline bool aligned(const void* ptr, size_t a) { return (reinterpret_cast<uintptr_t>(ptr) % a) == 0; }
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-device property of a kernel: remember what each
 // (device, kernel) pair already has, under a mutex (one process may drive several GPUs from several threads, as the

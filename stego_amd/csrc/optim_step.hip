@@ -23,6 +23,7 @@
 #include <cstdint>
 
 #include "../../include/stego_optim.h"
+#include "host_util.h"
 
 namespace {
 
@@ -175,9 +176,8 @@ __global__ __launch_bounds__(TPB) void adam_step_kernel(AdamParams p)
     }
 }
 
-inline int hip_rc(hipError_t e) { return e == hipSuccess ? STEGO_OK : STEGO_ERR_HIP + (int)e; }
-
-inline bool aligned(const void* ptr, size_t a) { return (reinterpret_cast<uintptr_t>(ptr) % a) == 0; }
+using stego::aligned;
+using stego::hip_rc;
 
 // Everything that can be checked without the buffers: the descriptor, then the table.  *n_chunks: the chunks of all segments.
 int check(const StegoAdamDesc* d, const StegoAdamSegment* segs, int64_t* n_chunks)

@@ -1,13 +1,17 @@
-// What the fused probe kernels share (probe_head.hip, probe_train.hip): torch's bilinear source index on the device and on the host,
-// the strided code load, and the largest source footprint of an output tile.
+// What the fused probe kernels share (probe_head.hip, confusion.hip, probe_train.hip): torch's bilinear source index on the device and
+// on the host, the strided code load, an output tile's source footprint on the device and its largest extent on the host, and the host's
+// tile plan of the probe head and the probe-confusion kernel.  The device phases those two kernels are built from: probe_phases.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 #include "../../include/stego_corr.h"
 
 namespace {
+
+constexpr int PROBE_TPB = 256;       // threads of a probe workgroup: one output pixel each
 
 inline __host__ __device__ int round4(int x) { return (x + 3) & ~3; }
 
@@ -25,6 +29,23 @@ __device__ inline void src_index(int dst, float scale, int in, int& i0, int& i1,
 __device__ inline float load_code(const StegoMap& m, int64_t b, int k, int y, int x)
 {
     return m.data[b * m.stride_n + (int64_t)k * m.stride_c + (int64_t)y * m.stride_h + (int64_t)x * m.stride_w];
+}
+
+// The source footprint of the output tile [Y0, Y1) x [X0, X1): first code row / column, rows and columns (no more than the host
+// planned room for), pixels.
+struct Footprint { int ya, xa, nr, nc, npx; };
+
+__device__ __forceinline__ Footprint tile_footprint(int Y0, int Y1, int X0, int X1, float scale_h, float scale_w, int h, int w, int max_nr,
+                                                    int max_nc)
+{
+    int ya, yb, xa, xb, t0;
+    float tl;
+    src_index(Y0, scale_h, h, ya, t0, tl);
+    src_index(Y1 - 1, scale_h, h, t0, yb, tl);
+    src_index(X0, scale_w, w, xa, t0, tl);
+    src_index(X1 - 1, scale_w, w, t0, xb, tl);
+    const int nr = min(yb - ya + 1, max_nr), nc = min(xb - xa + 1, max_nc);
+    return Footprint{ya, xa, nr, nc, nr * nc};
 }
 
 // Host mirror of src_index (plain float arithmetic); plan() adds one row / column of margin for a contraction the device may apply.
@@ -47,6 +68,42 @@ int max_span(int out, int in, float scale, int T)
         best = b - a + 1 > best ? b - a + 1 : best;
     }
     return best + 1 < in ? best + 1 : in;
+}
+
+// Label slots of a kernel instantiation: the probes' larger live label count n, rounded up to 8, 16, 32 or 64.
+inline int label_slots(int n) { return n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64; }
+
+// The tile of the probe head and the probe-confusion kernel: TY x TX <= PROBE_TPB output pixels, halved (rows first) until the largest
+// footprint - KS floats of code and NPS of projections per pixel - and the caller's `extra` bytes of LDS fit `budget` together.
+struct TilePlan {
+    int TY, TX, max_nr, max_nc, K4, KS, NMAX, NPS;
+    float scale_h, scale_w;
+    size_t lds;
+};
+
+TilePlan plan_tile(int K, int h, int w, int H, int W, int n, size_t extra, size_t budget)
+{
+    TilePlan pl{};
+    pl.scale_h = (float)h / (float)H;
+    pl.scale_w = (float)w / (float)W;
+    pl.K4 = round4(K);
+    pl.KS = pl.K4 + 4;
+    pl.NMAX = label_slots(n);
+    pl.NPS = 2 * pl.NMAX + 4;
+    pl.TX = W < 64 ? W : 64;
+    pl.TY = PROBE_TPB / pl.TX;
+    pl.TY = pl.TY < H ? pl.TY : H;
+    for (;;) {
+        pl.max_nr = max_span(H, h, pl.scale_h, pl.TY);
+        pl.max_nc = max_span(W, w, pl.scale_w, pl.TX);
+        pl.lds = (size_t)pl.max_nr * pl.max_nc * (pl.KS + pl.NPS) * sizeof(float) + extra;
+        if (pl.lds <= budget || (pl.TY == 1 && pl.TX == 1)) break;
+        if (pl.TY > 1)
+            pl.TY = (pl.TY + 1) / 2;
+        else
+            pl.TX = (pl.TX + 1) / 2;
+    }
+    return pl;
 }
 
 }  // namespace

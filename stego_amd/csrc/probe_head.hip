@@ -11,6 +11,7 @@
 //      K-channel code (four taps from LDS, no Gram form that could cancel), then the per-probe softmax and its store.
 // The tile is planned on the host so that the largest footprint fits 64 KiB of LDS (4 x 64 pixels, one per thread, at 8x upsampling;
 // smaller tiles for strong downsampling); every output offset is 64-bit.  No atomics: repeat launches give the same bits.
+// The phases themselves are in probe_phases.h, shared with confusion.hip's kernel; finish() and its three stores are this file's own.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,11 +19,12 @@
 #include <cstdint>
 
 #include "../../include/stego_probe.h"
-#include "probe_common.h"
+#include "host_util.h"
+#include "probe_phases.h"
 
 namespace {
 
-constexpr int TPB = 256;
+constexpr int TPB = PROBE_TPB;
 constexpr size_t LDS_BUDGET = 64 * 1024;
 
 struct ProbeParams {
@@ -40,18 +42,13 @@ struct ProbeParams {
     int32_t NPS;                     // LDS floats per footprint pixel of projections: 2 * NMAX label slots + 4
 };
 
-// The softmax of one probe at one pixel: l[0, n) are the logits, l[n, NMAX) are -inf (the label mask), so the max, the sums
-// (exp(-inf - m) adds +0) and the argmax over all NMAX slots are those over [0, n) with no per-label test; only the stores test
-// `j < n`.
+// The softmax of one probe at one pixel and its store: l[0, n) are the logits, l[n, NMAX) are -inf (the label mask); only the stores
+// test `j < n`.
 template <int NMAX>
 __device__ inline void finish(const float (&l)[NMAX], int n, int kind, void* out, int64_t b, int64_t HW, int64_t pix)
 {
-    float m = l[0];
-#pragma unroll
-    for (int j = 1; j < NMAX; ++j) m = fmaxf(m, l[j]);
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < NMAX; ++j) s += expf(l[j] - m);
+    float m, s;
+    softmax_stats<NMAX>(l, m, s);
     if (kind == STEGO_PROBE_PROBS) {
         float* o = static_cast<float*>(out) + b * n * HW + pix;
 #pragma unroll
@@ -71,16 +68,7 @@ __device__ inline void finish(const float (&l)[NMAX], int n, int kind, void* out
         }
         return;
     }
-    // ARGMAX: the first maximum of the very values LOG_PROBS writes (rounding can tie two distinct logits there); -inf never wins
-    int best = 0;
-    float bv = (l[0] - m) - ls;
-#pragma unroll
-    for (int j = 1; j < NMAX; ++j) {
-        const float v = (l[j] - m) - ls;
-        best = v > bv ? j : best;
-        bv = v > bv ? v : bv;
-    }
-    static_cast<int64_t*>(out)[b * HW + pix] = best;
+    static_cast<int64_t*>(out)[b * HW + pix] = first_max<NMAX>(l, m, ls);      // ARGMAX
 }
 
 template <int NMAX>
@@ -94,50 +82,16 @@ __global__ __launch_bounds__(TPB) void probe_head_kernel(ProbeParams p)
     const int64_t b = blockIdx.z;
     const int Y0 = blockIdx.y * p.TY, X0 = blockIdx.x * p.TX;
     const int Y1 = min(Y0 + p.TY, p.H), X1 = min(X0 + p.TX, p.W);
-    int ya, yb, xa, xb, t0;
-    float tl;
-    src_index(Y0, p.scale_h, p.h, ya, t0, tl);
-    src_index(Y1 - 1, p.scale_h, p.h, t0, yb, tl);
-    src_index(X0, p.scale_w, p.w, xa, t0, tl);
-    src_index(X1 - 1, p.scale_w, p.w, t0, xb, tl);
-    const int nr = min(yb - ya + 1, p.max_nr), nc = min(xb - xa + 1, p.max_nc);
-    const int npx = nr * nc;
+    const Footprint f = tile_footprint(Y0, Y1, X0, X1, p.scale_h, p.scale_w, p.h, p.w, p.max_nr, p.max_nc);
 
-    // 1. the footprint's code, flip-averaged, channels K .. K4 zeroed
-    for (int i = threadIdx.x; i < npx * p.K4; i += TPB) {
-        const int k = i % p.K4, px = i / p.K4;
-        const int y = ya + px / nc, x = xa + px % nc;
-        float v = 0.f;
-        if (k < p.K) {
-            v = load_code(p.code, b, k, y, x);
-            if (p.flip.data) v = (v + load_code(p.flip, b, k, y, p.w - 1 - x)) * 0.5f;
-        }
-        cs[px * p.KS + k] = v;
-    }
+    // 1. the footprint's code
+    load_footprint(cs, p.code, p.flip, p.flip.data != nullptr, b, f, p.K, p.K4, p.KS, p.w);
     __syncthreads();
 
-    // 2. projections: label slot j of both probes (linear slots [0, NMAX), cluster slots [NMAX, 2 NMAX)), one wave per slot
+    // 2. its projections onto both probes, and the label mask
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (threadIdx.x < 2 * NMAX) {
-        const int j = threadIdx.x;
-        mask[j] = (j < NMAX ? j < p.n_lin : j - NMAX < p.n_clu) ? 0.f : -INFINITY;
-    }
-    for (int j = wave; j < 2 * NMAX; j += TPB / 64) {
-        const bool lin = j < NMAX;
-        const int jj = lin ? j : j - NMAX;
-        const bool live = lin ? jj < p.n_lin : jj < p.n_clu;
-        const float* row = live ? (lin ? p.lin_w : p.cent) + (size_t)jj * p.K : nullptr;
-        const float bias = live && lin ? p.lin_b[jj] : 0.f;
-        for (int px = lane; px < npx; px += 64) {
-            float acc = 0.f;
-            if (live) {
-                const float* c = cs + px * p.KS;
-                for (int k = 0; k < p.K; ++k) acc = fmaf(row[k], c[k], acc);
-                acc += bias;
-            }
-            ps[px * p.NPS + j] = acc;
-        }
-    }
+    init_mask<NMAX>(mask, p.n_lin, p.n_clu);
+    project<NMAX>(ps, cs, p.lin_w, p.lin_b, p.cent, p.n_lin, p.n_clu, p.K, p.KS, p.NPS, f.npx, wave, lane);
     __syncthreads();
 
     // 3. output pixels
@@ -150,64 +104,25 @@ __global__ __launch_bounds__(TPB) void probe_head_kernel(ProbeParams p)
         const int i = threadIdx.x;
         const int Y = Y0 + i / p.TX, X = X0 + i % p.TX;
         if (i >= p.TY * p.TX || Y >= Y1 || X >= X1) return;
-        int y0, y1, x0, x1;
-        float h1, w1;
-        src_index(Y, p.scale_h, p.h, y0, y1, h1);
-        src_index(X, p.scale_w, p.w, x0, x1, w1);
-        const float h0 = 1.f - h1, w0 = 1.f - w1;
-        // (clamps: memory safety only - the footprint covers every tap, the host plan one row / column more)
-        const int r0 = max(min(y0 - ya, nr - 1), 0), r1 = max(min(y1 - ya, nr - 1), 0);
-        const int c0 = max(min(x0 - xa, nc - 1), 0), c1 = max(min(x1 - xa, nc - 1), 0);
-        const int q00 = r0 * nc + c0, q01 = r0 * nc + c1, q10 = r1 * nc + c0, q11 = r1 * nc + c1;
+        const Taps t = pixel_taps(Y, X, p.scale_h, p.scale_w, p.h, p.w, f);
         const int64_t pix = (int64_t)Y * p.W + X;
 
         if (p.lin_kind != STEGO_PROBE_SKIP) {
             float l[NMAX];
-#pragma unroll
-            for (int g = 0; g < NMAX / 4; ++g) {
-                const float4 a = ps4[q00 * NPS4 + g], bq = ps4[q01 * NPS4 + g], c = ps4[q10 * NPS4 + g], d = ps4[q11 * NPS4 + g];
-                const float4 mk = mask4[g];
-                l[4 * g + 0] = (h0 * (w0 * a.x + w1 * bq.x) + h1 * (w0 * c.x + w1 * d.x)) + mk.x;
-                l[4 * g + 1] = (h0 * (w0 * a.y + w1 * bq.y) + h1 * (w0 * c.y + w1 * d.y)) + mk.y;
-                l[4 * g + 2] = (h0 * (w0 * a.z + w1 * bq.z) + h1 * (w0 * c.z + w1 * d.z)) + mk.z;
-                l[4 * g + 3] = (h0 * (w0 * a.w + w1 * bq.w) + h1 * (w0 * c.w + w1 * d.w)) + mk.w;
-            }
+            linear_logits<NMAX>(l, ps4, mask4, NPS4, t);
             finish<NMAX>(l, p.n_lin, p.lin_kind, p.lin_out, b, HW, pix);
         }
         if (p.clu_kind != STEGO_PROBE_SKIP) {
-            // F.normalize's denominator: the norm of the interpolated code, clamped at 1e-12
-            float4 n4 = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int k4 = 0; k4 < (p.K4 >> 2); ++k4) {
-                const float4 a = cs4[q00 * KS4 + k4], bq = cs4[q01 * KS4 + k4], c = cs4[q10 * KS4 + k4], d = cs4[q11 * KS4 + k4];
-                const float vx = h0 * (w0 * a.x + w1 * bq.x) + h1 * (w0 * c.x + w1 * d.x);
-                const float vy = h0 * (w0 * a.y + w1 * bq.y) + h1 * (w0 * c.y + w1 * d.y);
-                const float vz = h0 * (w0 * a.z + w1 * bq.z) + h1 * (w0 * c.z + w1 * d.z);
-                const float vw = h0 * (w0 * a.w + w1 * bq.w) + h1 * (w0 * c.w + w1 * d.w);
-                n4.x = fmaf(vx, vx, n4.x);
-                n4.y = fmaf(vy, vy, n4.y);
-                n4.z = fmaf(vz, vz, n4.z);
-                n4.w = fmaf(vw, vw, n4.w);
-            }
-            const float den = fmaxf(sqrtf((n4.x + n4.y) + (n4.z + n4.w)), 1e-12f);
+            const float den = code_norm(cs4, KS4, p.K4, t);
             float l[NMAX];
-#pragma unroll
-            for (int g = 0; g < NMAX / 4; ++g) {
-                const int o = NMAX / 4 + g;
-                const float4 a = ps4[q00 * NPS4 + o], bq = ps4[q01 * NPS4 + o], c = ps4[q10 * NPS4 + o], d = ps4[q11 * NPS4 + o];
-                const float4 mk = mask4[o];
-                l[4 * g + 0] = (h0 * (w0 * a.x + w1 * bq.x) + h1 * (w0 * c.x + w1 * d.x)) / den * p.alpha + mk.x;
-                l[4 * g + 1] = (h0 * (w0 * a.y + w1 * bq.y) + h1 * (w0 * c.y + w1 * d.y)) / den * p.alpha + mk.y;
-                l[4 * g + 2] = (h0 * (w0 * a.z + w1 * bq.z) + h1 * (w0 * c.z + w1 * d.z)) / den * p.alpha + mk.z;
-                l[4 * g + 3] = (h0 * (w0 * a.w + w1 * bq.w) + h1 * (w0 * c.w + w1 * d.w)) / den * p.alpha + mk.w;
-            }
+            cluster_logits<NMAX>(l, ps4, mask4, NPS4, t, den, p.alpha);
             finish<NMAX>(l, p.n_clu, p.clu_kind, p.clu_out, b, HW, pix);
         }
     }
 }
 
-inline int hip_rc(hipError_t e) { return e == hipSuccess ? STEGO_OK : STEGO_ERR_HIP + (int)e; }
-
-inline bool aligned(const void* ptr, size_t a) { return (reinterpret_cast<uintptr_t>(ptr) % a) == 0; }
+using stego::aligned;
+using stego::hip_rc;
 
 inline bool kind_ok(int k) { return k >= STEGO_PROBE_SKIP && k <= STEGO_PROBE_ARGMAX; }
 
@@ -225,36 +140,10 @@ int check_desc(const StegoProbeDesc* d)
     return STEGO_OK;
 }
 
-struct Plan {
-    int TY, TX, max_nr, max_nc, K4, KS, NMAX, NPS;
-    float scale_h, scale_w;
-    size_t lds;
-};
-
-Plan plan(const StegoProbeDesc* d)
+TilePlan plan(const StegoProbeDesc* d)
 {
-    Plan pl{};
-    pl.scale_h = (float)d->h / (float)d->H;
-    pl.scale_w = (float)d->w / (float)d->W;
-    pl.K4 = round4(d->K);
-    pl.KS = pl.K4 + 4;
     const int n = std::max(d->lin_kind != STEGO_PROBE_SKIP ? d->n_lin : 0, d->clu_kind != STEGO_PROBE_SKIP ? d->n_clu : 0);
-    pl.NMAX = n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64;
-    pl.NPS = 2 * pl.NMAX + 4;
-    pl.TX = d->W < 64 ? d->W : 64;
-    pl.TY = TPB / pl.TX;
-    pl.TY = pl.TY < d->H ? pl.TY : d->H;
-    for (;;) {
-        pl.max_nr = max_span(d->H, d->h, pl.scale_h, pl.TY);
-        pl.max_nc = max_span(d->W, d->w, pl.scale_w, pl.TX);
-        pl.lds = ((size_t)pl.max_nr * pl.max_nc * (pl.KS + pl.NPS) + 2 * pl.NMAX) * sizeof(float);
-        if (pl.lds <= LDS_BUDGET || (pl.TY == 1 && pl.TX == 1)) break;
-        if (pl.TY > 1)
-            pl.TY = (pl.TY + 1) / 2;
-        else
-            pl.TX = (pl.TX + 1) / 2;
-    }
-    return pl;
+    return plan_tile(d->K, d->h, d->w, d->H, d->W, n, 2 * label_slots(n) * sizeof(float), LDS_BUDGET);     // + the label mask
 }
 
 }  // namespace
@@ -262,7 +151,7 @@ Plan plan(const StegoProbeDesc* d)
 extern "C" size_t stego_probe_head_plan(const StegoProbeDesc* desc, int32_t* tile_rows, int32_t* tile_cols)
 {
     if (check_desc(desc) != STEGO_OK) return 0;
-    const Plan pl = plan(desc);
+    const TilePlan pl = plan(desc);
     if (tile_rows) *tile_rows = pl.TY;
     if (tile_cols) *tile_cols = pl.TX;
     return pl.lds;
@@ -281,7 +170,7 @@ extern "C" int stego_probe_head(const StegoProbeDesc* desc, const StegoMap* code
         return STEGO_ERR_ALIGN;
     if (clu && (!aligned(centroids, 4) || !aligned(clu_out, desc->clu_kind == STEGO_PROBE_ARGMAX ? 8 : 4))) return STEGO_ERR_ALIGN;
 
-    const Plan pl = plan(desc);
+    const TilePlan pl = plan(desc);
     ProbeParams p{};
     p.code = *code;
     p.flip = code_flip ? *code_flip : StegoMap{nullptr, 0, 0, 0, 0};

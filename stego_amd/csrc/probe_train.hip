@@ -213,14 +213,8 @@ __global__ __launch_bounds__(TPB) void probe_train_kernel(TrainParams)
             const int trem = (int)(tile - b * tiles_per_image);
             const int Y0 = (trem / p.tiles_x) * p.TY, X0 = (trem % p.tiles_x) * p.TX;
             const int Y1 = min(Y0 + p.TY, p.H), X1 = min(X0 + p.TX, p.W);
-            int ya, yb, xa, xb, t0;
-            float tl;
-            src_index(Y0, p.scale_h, p.h, ya, t0, tl);
-            src_index(Y1 - 1, p.scale_h, p.h, t0, yb, tl);
-            src_index(X0, p.scale_w, p.w, xa, t0, tl);
-            src_index(X1 - 1, p.scale_w, p.w, t0, xb, tl);
-            const int nr = min(yb - ya + 1, p.max_nr), nc = min(xb - xa + 1, p.max_nc);
-            const int npx = nr * nc;
+            const Footprint f = tile_footprint(Y0, Y1, X0, X1, p.scale_h, p.scale_w, p.h, p.w, p.max_nr, p.max_nc);
+            const int ya = f.ya, xa = f.xa, nr = f.nr, nc = f.nc, npx = f.npx;
             long long lab = -1;                  // this thread's label pixel, asked for now and used in step 3
             if (t < p.TY * p.TX) {
                 const int Y = Y0 + t / p.TX, X = X0 + t % p.TX;
@@ -585,9 +579,8 @@ __global__ __launch_bounds__(TPB) void probe_train_reduce(ReduceParams p)
     }
 }
 
-inline int hip_rc(hipError_t e) { return e == hipSuccess ? STEGO_OK : STEGO_ERR_HIP + (int)e; }
-
-inline bool aligned(const void* ptr, size_t a) { return (reinterpret_cast<uintptr_t>(ptr) % a) == 0; }
+using stego::aligned;
+using stego::hip_rc;
 
 int check_desc(const StegoProbeTrainDesc* d)
 {
@@ -617,7 +610,7 @@ Plan plan(const StegoProbeTrainDesc* d)
     pl.scale_w = (float)d->w / (float)d->W;
     pl.KS = (d->K + 1) | 1;
     const int n = std::max(d->n_lin, d->n_clu);
-    pl.NMAX = n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64;
+    pl.NMAX = label_slots(n);
     pl.NPS = pl.NMAX + 4;
     pl.NG = pl.NMAX + 1;
     pl.TX = d->W < 64 ? d->W : 64;
