@@ -83,6 +83,21 @@ PROBE_KINDS = {None: PROBE_SKIP, "log_probs": PROBE_LOG_PROBS, "probs": PROBE_PR
 PROBE_MAX_K, PROBE_MAX_N, PROBE_MAX_OUT = 128, 64, 2048
 
 
+class StegoWindowLayout(Structure):
+    """include/stego_stitch.h"""
+    _fields_ = [(n, c_int32) for n in ("H", "W", "win", "stride")]
+
+
+class StegoStitchDesc(Structure):
+    """include/stego_stitch.h"""
+    _fields_ = [("layout", StegoWindowLayout)] + \
+        [(n, c_int32) for n in ("T", "K", "hc", "wc", "n_lin", "n_clu", "lin_kind", "clu_kind")] + [("alpha", c_float)]
+
+
+STITCH_ERR_DIM, STITCH_ERR_SIZE, STITCH_ERR_LAYOUT, STITCH_ERR_WINDOWS, STITCH_ERR_OUTPUT, STITCH_ERR_RANGE = 120, 121, 122, 123, 124, 125
+STITCH_MAX_SIDE = 32768
+
+
 class StegoProbeConfusionDesc(Structure):
     """include/stego_confusion.h"""
     _fields_ = [(n, c_int32) for n in ("B", "K", "h", "w", "H", "W", "n_lin", "n_clu", "lin_on", "clu_on")] + \
@@ -203,6 +218,9 @@ SIGNATURES = {
     "stego_data_prepare": (c_int32, [POINTER(StegoDataDesc)] + [_P] * 10 + [_P]),
     "stego_probe_head": (c_int32, [POINTER(StegoProbeDesc), _M, _M] + [_P] * 5 + [_P]),
     "stego_probe_head_plan": (c_size_t, [POINTER(StegoProbeDesc), POINTER(c_int32), POINTER(c_int32)]),
+    "stego_stitch_probe": (c_int32, [POINTER(StegoStitchDesc), _M, _M] + [_P] * 5 + [_P]),
+    "stego_stitch_probe_plan": (c_size_t, [POINTER(StegoStitchDesc)] + [POINTER(c_int32)] * 4),
+    "stego_window_gather": (c_int32, [POINTER(StegoWindowLayout), _M, c_int32, c_int32, _P, _P, _P]),
     "stego_probe_confusion": (c_int32, [POINTER(StegoProbeConfusionDesc), _M, _M] + [_P] * 6 + [_P]),
     "stego_probe_confusion_plan": (c_size_t, [POINTER(StegoProbeConfusionDesc), POINTER(c_int32), POINTER(c_int32)]),
     "stego_confusion": (c_int32, [POINTER(StegoConfusionDesc), _P, _P, _P, _P]),
@@ -1151,6 +1169,97 @@ def probe_head(code, code_flip, lin_w, lin_b, centroids, size, lin_kind, clu_kin
     with _on_device(dev):
         _check(probe_head_raw(desc, _map(code), _map(code_flip) if code_flip is not None else None, lw, lb, ce, lo, co, _stream()))
     return lo, co
+
+
+# ---- sliding windows stitched on the canvas (include/stego_stitch.h; stego_amd.segment.segment_large wraps them for a model)
+def window_layout(H, W, win, stride):
+    return StegoWindowLayout(int(H), int(W), int(win), int(stride))
+
+
+def stitch_desc(H, W, win, stride, T, K, hc, wc, n_lin, n_clu, lin_kind, clu_kind, alpha):
+    return StegoStitchDesc(window_layout(H, W, win, stride), int(T), int(K), int(hc), int(wc), int(n_lin), int(n_clu), int(lin_kind),
+                           int(clu_kind), float(alpha))
+
+
+def stitch_probe_plan(desc):
+    """stego_stitch_probe_plan (host only) -> (LDS bytes, tile rows, tile columns, ny, nx); 0 bytes for an invalid descriptor."""
+    ty, tx, ny, nx = c_int32(0), c_int32(0), c_int32(0), c_int32(0)
+    n = load().stego_stitch_probe_plan(byref(desc), byref(ty), byref(tx), byref(ny), byref(nx))
+    return int(n), ty.value, tx.value, ny.value, nx.value
+
+
+def stitch_probe_raw(desc, code, code_flip, lin_w, lin_b, centroids, lin_out, clu_out, stream=None):
+    """stego_stitch_probe with every argument given: `code` / `code_flip` are StegoMap (or None), the rest raw addresses or tensors
+    (tests: the error codes) -> the return code, unchecked."""
+    def addr(x):
+        return _ptr(x) if torch.is_tensor(x) else x
+    return int(load().stego_stitch_probe(byref(desc) if desc is not None else None, byref(code) if code is not None else None,
+                                         byref(code_flip) if code_flip is not None else None, addr(lin_w), addr(lin_b), addr(centroids),
+                                         addr(lin_out), addr(clu_out), stream if stream is not None else None))
+
+
+def stitch_probe(code, code_flip, lin_w, lin_b, centroids, size, win, stride, lin_kind, clu_kind, alpha):
+    """stego_stitch_probe: the codes of the canvas's windows (and of their mirror images, or None) float32 [T, K, hc, wc] with any
+    strides, window t = iy * nx + ix at index t; the probes' weights as for probe_head; `size` = (H, W) of the canvas, `win` and
+    `stride` its window layout -> (linear output, cluster output) on the canvas, each None for a skipped probe, float32 [n, H, W] for
+    "log_probs" / "probs" and int64 [H, W] for "argmax"."""
+    _require_dev(code, code_flip, lin_w, lin_b, centroids)
+    T, K, hc, wc = code.shape
+    H, W = int(size[0]), int(size[1])
+    lk, ck = PROBE_KINDS[lin_kind], PROBE_KINDS[clu_kind]
+    n_lin = int(lin_w.shape[0]) if lk != PROBE_SKIP else 0
+    n_clu = int(centroids.shape[0]) if ck != PROBE_SKIP else 0
+    if code_flip is not None and tuple(code_flip.shape) != tuple(code.shape):
+        raise ValueError("code_flip %s does not match code %s" % (tuple(code_flip.shape), tuple(code.shape)))
+    dev = code.device
+
+    def out(kind, n):
+        if kind == PROBE_SKIP:
+            return None
+        if kind == PROBE_ARGMAX:
+            return torch.empty(H, W, dtype=torch.int64, device=dev)
+        return torch.empty(n, H, W, dtype=torch.float32, device=dev)
+
+    def weights(t, n):
+        return _dense(t, torch.float32) if t is not None and n else None
+    lw, lb, ce = weights(lin_w, n_lin), weights(lin_b, n_lin), weights(centroids, n_clu)
+    if lw is not None and tuple(lw.shape) != (n_lin, K) or ce is not None and tuple(ce.shape) != (n_clu, K):
+        raise ValueError("probe weights %s / %s do not match K = %d" % (None if lw is None else tuple(lw.shape),
+                                                                        None if ce is None else tuple(ce.shape), K))
+    desc = stitch_desc(H, W, win, stride, T, K, hc, wc, n_lin, n_clu, lk, ck, alpha)
+    if stitch_probe_plan(desc)[0] == 0:     # an invalid descriptor: name the error before any output is sized from it
+        _check(stitch_probe_raw(desc, None, None, None, None, None, None, None))
+    lo, co = out(lk, n_lin), out(ck, n_clu)
+    with _on_device(dev):
+        _check(stitch_probe_raw(desc, _map(code), _map(code_flip) if code_flip is not None else None, lw, lb, ce, lo, co, _stream()))
+    return lo, co
+
+
+def window_gather_raw(layout, img, t0, n, out, out_flip, stream=None):
+    """stego_window_gather with every argument given: `img` is a StegoMap (or None), `out` / `out_flip` raw addresses or tensors ->
+    the return code, unchecked."""
+    def addr(x):
+        return _ptr(x) if torch.is_tensor(x) else x
+    return int(load().stego_window_gather(byref(layout) if layout is not None else None, byref(img) if img is not None else None,
+                                          int(t0), int(n), addr(out), addr(out_flip), stream if stream is not None else None))
+
+
+def window_gather(img, win, stride, t0, n, flip=False):
+    """stego_window_gather: windows [t0, t0 + n) of the float32 image [3, H, W] (any strides) -> float32 [n, 3, win, win], and with
+    `flip` also their horizontal mirror images: (windows, mirrored windows)."""
+    _require_dev(img)
+    if img.dtype != torch.float32 or img.dim() != 3 or img.shape[0] != 3:
+        raise ValueError("img: expected a float32 [3, H, W] tensor, got %s %s" % (img.dtype, tuple(img.shape)))
+    H, W = int(img.shape[1]), int(img.shape[2])
+    dev = img.device
+    layout = window_layout(H, W, win, stride)
+    shape = (max(int(n), 0), 3, max(int(win), 0), max(int(win), 0))
+    ok = load().stego_window_gather(byref(layout), None, int(t0), int(n), None, None, None) == 1       # only the pointers are missing
+    out = torch.empty(shape if ok else (0,), dtype=torch.float32, device=dev)
+    out_flip = torch.empty(shape if ok else (0,), dtype=torch.float32, device=dev) if flip else None
+    with _on_device(dev):
+        _check(window_gather_raw(layout, _map(img.unsqueeze(0)), t0, n, out, out_flip, _stream()))
+    return (out, out_flip) if flip else out
 
 
 # ---- device-side confusion matrices (include/stego_confusion.h; stego_amd.metrics wraps them for the trainer and evaluate())

@@ -17,6 +17,7 @@
 #include "../../include/stego_aug.h"
 #include "../../include/stego_confusion.h"
 #include "../../include/stego_optim.h"
+#include "../../include/stego_stitch.h"
 #include "corr_wide.h"
 
 namespace stego {
@@ -403,6 +404,12 @@ const char* stego_error_string(int code)
         case STEGO_ERR_OPTIM_SEGMENT: return "fused Adam: a segment with count < 1, a group index out of range, or a gradient or state slice outside its buffer";
         case STEGO_ERR_OPTIM_PARAM: return "fused Adam: a beta outside [0, 1), or lr or eps negative or not finite";
         case STEGO_ERR_OPTIM_FLAGS: return "fused Adam: zero_grads or a group's active flag neither 0 nor 1, or no active group";
+        case STEGO_ERR_STITCH_DIM: return "stitch: K outside [1, 128] or an active probe's labels outside [1, 64] (include/stego_stitch.h)";
+        case STEGO_ERR_STITCH_SIZE: return "stitch: a canvas side outside [1, 32768], the window side outside [1, 2048] or a code side outside [1, 65535]";
+        case STEGO_ERR_STITCH_LAYOUT: return "stitch: the window is larger than the canvas, or the stride is outside win <= 2 * stride <= 2 * win";
+        case STEGO_ERR_STITCH_WINDOWS: return "stitch: T is not the layout's ny * nx windows";
+        case STEGO_ERR_STITCH_OUTPUT: return "stitch: unknown output kind, or both probes skipped";
+        case STEGO_ERR_STITCH_RANGE: return "stitch: window_gather's t0 < 0, n outside [1, 65535] or t0 + n beyond the layout's windows";
         case STEGO_ERR_CRF_RANGE: return "dense CRF: a lattice coordinate would leave the packed key (image too large for its standard deviations)";
         default: return code >= STEGO_ERR_HIP ? "HIP runtime error (code - 1000 = hipError_t)" : "unknown error";
     }

@@ -11,7 +11,8 @@
 //      K-channel code (four taps from LDS, no Gram form that could cancel), then the per-probe softmax and its store.
 // The tile is planned on the host so that the largest footprint fits 64 KiB of LDS (4 x 64 pixels, one per thread, at 8x upsampling;
 // smaller tiles for strong downsampling); every output offset is 64-bit.  No atomics: repeat launches give the same bits.
-// The phases themselves are in probe_phases.h, shared with confusion.hip's kernel; finish() and its three stores are this file's own.
+// The phases themselves are in probe_phases.h, shared with confusion.hip's and stitch_probe.hip's kernels; finish() and its three stores
+// are there too, shared with stitch_probe.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -41,35 +42,6 @@ struct ProbeParams {
     int32_t K4, KS;                  // K rounded up to 4; LDS floats per footprint pixel of code
     int32_t NPS;                     // LDS floats per footprint pixel of projections: 2 * NMAX label slots + 4
 };
-
-// The softmax of one probe at one pixel and its store: l[0, n) are the logits, l[n, NMAX) are -inf (the label mask); only the stores
-// test `j < n`.
-template <int NMAX>
-__device__ inline void finish(const float (&l)[NMAX], int n, int kind, void* out, int64_t b, int64_t HW, int64_t pix)
-{
-    float m, s;
-    softmax_stats<NMAX>(l, m, s);
-    if (kind == STEGO_PROBE_PROBS) {
-        float* o = static_cast<float*>(out) + b * n * HW + pix;
-#pragma unroll
-        for (int j = 0; j < NMAX; ++j) {
-            if (j < n) *o = expf(l[j] - m) / s;
-            o += HW;
-        }
-        return;
-    }
-    const float ls = logf(s);
-    if (kind == STEGO_PROBE_LOG_PROBS) {
-        float* o = static_cast<float*>(out) + b * n * HW + pix;
-#pragma unroll
-        for (int j = 0; j < NMAX; ++j) {
-            if (j < n) *o = (l[j] - m) - ls;
-            o += HW;
-        }
-        return;
-    }
-    static_cast<int64_t*>(out)[b * HW + pix] = first_max<NMAX>(l, m, ls);      // ARGMAX
-}
 
 template <int NMAX>
 __global__ __launch_bounds__(TPB) void probe_head_kernel(ProbeParams p)

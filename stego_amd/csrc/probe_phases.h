@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "../../include/stego_probe.h"
 #include "probe_common.h"
 
 namespace {
@@ -173,6 +174,35 @@ __device__ __forceinline__ int first_max(const float (&l)[NMAX])
     float m, s;
     softmax_stats<NMAX>(l, m, s);
     return first_max<NMAX>(l, m, logf(s));
+}
+
+// The softmax of one probe at one pixel and its store (probe_head.hip's and stitch_probe.hip's sink; `kind` is a STEGO_PROBE_*): l[0, n) are the logits, l[n, NMAX) are -inf (the label mask); only the stores
+// test `j < n`.
+template <int NMAX>
+__device__ inline void finish(const float (&l)[NMAX], int n, int kind, void* out, int64_t b, int64_t HW, int64_t pix)
+{
+    float m, s;
+    softmax_stats<NMAX>(l, m, s);
+    if (kind == STEGO_PROBE_PROBS) {
+        float* o = static_cast<float*>(out) + b * n * HW + pix;
+#pragma unroll
+        for (int j = 0; j < NMAX; ++j) {
+            if (j < n) *o = expf(l[j] - m) / s;
+            o += HW;
+        }
+        return;
+    }
+    const float ls = logf(s);
+    if (kind == STEGO_PROBE_LOG_PROBS) {
+        float* o = static_cast<float*>(out) + b * n * HW + pix;
+#pragma unroll
+        for (int j = 0; j < NMAX; ++j) {
+            if (j < n) *o = (l[j] - m) - ls;
+            o += HW;
+        }
+        return;
+    }
+    static_cast<int64_t*>(out)[b * HW + pix] = first_max<NMAX>(l, m, ls);      // ARGMAX
 }
 
 }  // namespace

@@ -128,6 +128,17 @@ def image_transform(res, crop="center"):
     return f
 
 
+def full_image_transform(res):
+    """The image at its own size for sliding-window segmentation (stego_amd.segment.segment_large): no crop, and no resize unless the
+    shorter side is below `res` (then Resize(res, NEAREST) as in image_transform, so that one window fits); ToTensor, Normalize."""
+    def f(im):
+        if min(im.size) < res:
+            im = _resize(im, res)
+        x = np.asarray(im, dtype=np.float32) / np.float32(255.0)
+        return torch.from_numpy(((x - _MEAN) / _STD).transpose(2, 0, 1).copy())
+    return f
+
+
 def label_transform(res, crop="center"):
     """get_transform(res, True, crop): resize + crop, ToTargetTensor (int64 [1, res, res])."""
     rc = _cropper(crop)

@@ -7,6 +7,10 @@ Each batch goes through stego_amd.segment.segment: the backbone on the images an
 (csrc/probe_head.hip) and the dense CRF on the device.  Deviations from the reference: a prediction is named after the file's stem
 (os.path.splitext, the reference's name for every file with an extension), files PIL cannot open are skipped and named instead of
 ending the run, the files are read in sorted order, and DataParallel (`use_ddp`) is not supported.
+
+With `full_res=True` no file is cropped or shrunk: each goes through stego_amd.segment.segment_large at its own size, as overlapping
+res x res windows `window_stride` apart (default: half a window) stitched on the device (csrc/stitch_probe.hip), and its PNGs have the
+image's size.  A file whose shorter side is below `res` is first resized so that it equals `res`.
 """
 import os
 import sys
@@ -16,8 +20,8 @@ import numpy as np
 import torch
 from PIL import Image
 
-from .data import image_transform
-from .segment import segment
+from .data import full_image_transform, image_transform
+from .segment import segment, segment_large
 from .train_segmentation import LitUnsupervisedSegmenter, load_config
 
 DEMO_CONFIG = join(dirname(__file__), "configs", "demo_config.yml")
@@ -53,6 +57,11 @@ def collate(items):
     return imgs, [name for _, name in good], bad
 
 
+def first(items):
+    """collate_fn of the full-resolution run: one file per batch, nothing stacked."""
+    return items[0]
+
+
 def result_dir(cfg):
     return join(cfg.output_root, "results", "predictions", cfg.experiment_name)
 
@@ -78,20 +87,39 @@ def my_app(cfg):
     dev = torch.device("cuda", 0)
     model = LitUnsupervisedSegmenter.load_from_checkpoint(cfg.model_path)
     model.eval().to(dev)
+    run_crf = getattr(cfg, "run_crf", True)
+    written, skipped = [], []
+
+    def save(name, linear, cluster):
+        for sub, pred in (("linear", linear), ("cluster", cluster)):
+            path = join(out, sub, prediction_name(name))
+            Image.fromarray(pred.astype(np.uint8)).save(path)          # 2-D uint8: mode "L"
+            written.append(path)
+
+    if getattr(cfg, "full_res", False):
+        dataset = UnlabeledImageFolder(cfg.image_dir, full_image_transform(cfg.res))
+        loader = torch.utils.data.DataLoader(dataset, 1, shuffle=False, num_workers=cfg.num_workers, collate_fn=first)
+        for img, name in loader:
+            if img is None:
+                skipped.append(name)
+                continue
+            linear, cluster = segment_large(model, img.to(dev), window=cfg.res, stride=getattr(cfg, "window_stride", None),
+                                            batch=cfg.batch_size * 2, run_crf=run_crf)
+            save(name, linear.cpu().numpy(), cluster.cpu().numpy())
+        if skipped:
+            print("skipped %d file(s) PIL cannot read: %s" % (len(skipped), ", ".join(skipped)))
+        return written
+
     dataset = UnlabeledImageFolder(cfg.image_dir, image_transform(cfg.res, "center"))
     loader = torch.utils.data.DataLoader(dataset, cfg.batch_size * 2, shuffle=False, num_workers=cfg.num_workers, collate_fn=collate)
-    written, skipped = [], []
     for imgs, names, bad in loader:
         skipped.extend(bad)
         if imgs is None:
             continue
-        linear, cluster = segment(model, imgs.to(dev), run_crf=getattr(cfg, "run_crf", True))
+        linear, cluster = segment(model, imgs.to(dev), run_crf=run_crf)
         linear, cluster = linear.cpu().numpy(), cluster.cpu().numpy()
         for j, name in enumerate(names):
-            for sub, pred in (("linear", linear[j]), ("cluster", cluster[j])):
-                path = join(out, sub, prediction_name(name))
-                Image.fromarray(pred.astype(np.uint8)).save(path)          # 2-D uint8: mode "L"
-                written.append(path)
+            save(name, linear[j], cluster[j])
     if skipped:
         print("skipped %d file(s) PIL cannot read: %s" % (len(skipped), ", ".join(skipped)))
     return written

@@ -4,12 +4,16 @@ The reference flip-averages the code, resizes it to the image's resolution with 
 (log-)softmax over full-resolution tensors.  Here csrc/probe_head.hip (include/stego_probe.h) does all of it in one launch from the
 low-resolution code, and writes per probe what the next step needs: the probabilities the dense CRF takes, the log-probabilities the
 metrics take, or the label map directly when the CRF is off.  There is no CPU path: CPU tensors raise.
+
+segment_large() segments an image of any size at least the window's: overlapping windows (include/stego_stitch.h) cut out on the device,
+run through the backbone in chunks, and stitched on the canvas by csrc/stitch_probe.hip in one launch that reads the windows' codes and
+writes only the canvas.  The reference's plot_potsdam.py tiles 320-pixel windows without overlap, one by one, in Python.
 """
 import torch
 import torch.nn.functional as F
 
 from . import capi
-from .crf import _device_tensor, dense_crf_batch, image_to_bgr_u8
+from .crf import Bi_RGB_STD, Bi_W, Bi_XY_STD, MAX_ITER, POS_W, POS_XY_STD, _device_tensor, dense_crf_batch, image_to_bgr_u8
 
 KINDS = ("log_probs", "probs", "argmax", None)
 
@@ -55,3 +59,87 @@ def segment(model, img, run_crf=True, flip=True, res=None):
             return lin, clu
         bgr = image_to_bgr_u8(img)
         return dense_crf_batch(bgr, lin).argmax(1), dense_crf_batch(bgr, clu).argmax(1)
+
+
+def window_origins(L, win, stride):
+    """Origins of the windows along an axis of length L (include/stego_stitch.h): n = 1 + ceil((L - win) / stride) windows at
+    min(i * stride, L - win); the last one is shifted back so that it ends at the edge."""
+    L, win, stride = int(L), int(win), int(stride)
+    if win < 1 or L < win or stride > win or 2 * stride < win:
+        raise ValueError("window_origins: need 1 <= win <= L and win <= 2 * stride <= 2 * win, got L = %d, win = %d, stride = %d"
+                         % (L, win, stride))
+    n = 1 + -((win - L) // stride)
+    return [min(i * stride, L - win) for i in range(n)]
+
+
+def _crf_fits(dev, n_labels, H, W):
+    """Raise when the dense CRF's workspace and its two [n, H, W] planes do not fit the free device memory."""
+    desc = capi.crf_desc(1, n_labels, H, W, MAX_ITER, POS_W, POS_XY_STD, Bi_W, Bi_XY_STD, Bi_RGB_STD)
+    need = capi.crf_workspace_bytes(desc)
+    if need == 0:
+        raise RuntimeError("segment_large: the dense CRF does not take a %d x %d canvas with %d labels; pass run_crf=False"
+                           % (H, W, n_labels))
+    need += 4 * n_labels * H * W            # the CRF's output beside the probabilities that are already there
+    free = torch.cuda.mem_get_info(dev)[0]
+    if need > free:
+        raise RuntimeError("segment_large: the dense CRF needs %.1f GiB for a %d x %d canvas with %d labels and %.1f GiB are free; "
+                           "pass run_crf=False" % (need / 2.0 ** 30, H, W, n_labels, free / 2.0 ** 30))
+
+
+def _segment_large_one(model, img, window, stride, batch, run_crf, flip):
+    H, W = int(img.shape[1]), int(img.shape[2])
+    T = len(window_origins(H, window, stride)) * len(window_origins(W, window, stride))
+    codes, codes_flip = [], []
+    for t0 in range(0, T, batch):
+        n = min(batch, T - t0)
+        wins = capi.window_gather(img, window, stride, t0, n, flip=flip)
+        if flip:
+            codes.append(model.net(wins[0])[1])
+            codes_flip.append(model.net(wins[1])[1])
+        else:
+            codes.append(model.net(wins)[1])
+    code = codes[0] if len(codes) == 1 else torch.cat(codes)
+    code_flip = None if not flip else (codes_flip[0] if len(codes_flip) == 1 else torch.cat(codes_flip))
+    lw = model.linear_probe.weight.detach()
+    lw = lw.reshape(lw.shape[0], lw.shape[1])
+    lb = model.linear_probe.bias.detach()
+    cent = F.normalize(model.cluster_probe.clusters.detach(), dim=1)
+    kind = "probs" if run_crf else "argmax"
+    if run_crf:
+        _crf_fits(img.device, max(int(lw.shape[0]), int(cent.shape[0])), H, W)
+    lin, clu = capi.stitch_probe(code.detach().float(), None if code_flip is None else code_flip.detach().float(), lw, lb, cent, (H, W),
+                                 window, stride, kind, kind, 2)
+    del codes, codes_flip, code, code_flip
+    if not run_crf:
+        return lin, clu
+    bgr = image_to_bgr_u8(img)
+    lin = dense_crf_batch(bgr, lin.unsqueeze(0)).argmax(1)[0]
+    return lin, dense_crf_batch(bgr, clu.unsqueeze(0)).argmax(1)[0]
+
+
+def segment_large(model, img, window, stride=None, batch=16, run_crf=True, flip=True):
+    """A normalised image [3, H, W] of any size with H, W >= window (or [B, 3, H, W], image by image) -> (linear_preds,
+    cluster_preds), int64 [H, W] (or [B, H, W]).  The image is cut into overlapping window x window pieces `stride` apart (default
+    ceil(window / 2); window <= 2 * stride <= 2 * window; the last window of a row or column is shifted back to end at the edge), the
+    windows - and their mirror images when `flip` - go through the backbone `batch` at a time, and one stitch_probe launch blends the
+    windows' logits per pixel with tent weights and writes the canvas: the label maps directly, or the probabilities for the dense
+    CRF (run_crf), which then runs on the whole canvas."""
+    if not torch.is_tensor(img):
+        raise TypeError("img: expected a torch tensor, got %s" % type(img).__name__)
+    if img.dim() not in (3, 4) or img.shape[-3] != 3:
+        raise ValueError("img: expected [3, H, W] or [B, 3, H, W], got %s" % (tuple(img.shape),))
+    window = int(window)
+    stride = (window + 1) // 2 if stride is None else int(stride)
+    H, W = int(img.shape[-2]), int(img.shape[-1])
+    if H < window or W < window:
+        raise ValueError("segment_large: the image (%d x %d) is smaller than the window (%d); resize it and use segment()" % (H, W, window))
+    if window < 1 or stride > window or 2 * stride < window:
+        raise ValueError("segment_large: need window <= 2 * stride <= 2 * window, got window = %d, stride = %d" % (window, stride))
+    if int(batch) < 1:
+        raise ValueError("segment_large: batch = %r" % (batch,))
+    _device_tensor(img, "img")
+    with torch.no_grad():
+        if img.dim() == 3:
+            return _segment_large_one(model, img.float(), window, stride, int(batch), run_crf, flip)
+        outs = [_segment_large_one(model, im.float(), window, stride, int(batch), run_crf, flip) for im in img]
+        return torch.stack([o[0] for o in outs]), torch.stack([o[1] for o in outs])
