@@ -19,37 +19,7 @@
 #include "../../include/stego_optim.h"
 #include "../../include/stego_stitch.h"
 #include "corr_wide.h"
-
-namespace stego {
-hipError_t launch_corr_sample(const SampleParams& prm, int precision, hipStream_t stream);
-hipError_t launch_corr_tile(const CorrParams& prm, int precision, hipStream_t stream);
-hipError_t launch_corr_finalize(const CorrParams& prm, hipStream_t stream);
-bool fused_supported(const FusedParams& prm, int precision);
-hipError_t launch_corr_fused(const FusedParams& prm, int precision, size_t sync_bytes, bool prepared, bool shared_device, hipStream_t stream, hipEvent_t* ev);
-hipError_t prepare_corr_fused(const FusedParams& prm, size_t sync_bytes, hipStream_t stream);
-hipError_t launch_fast_draws(const long long* seed, long long n_coord, int n_neg, int B, float* c1, float* c2, long long* perms,
-                             hipStream_t stream);
-hipError_t launch_finish_draws(const float* u1, const float* u2, long long n_coord, const long long* const* raw, int n_neg,
-                               int B, float* c1, float* c2, long long* perms, hipStream_t stream);
-hipError_t launch_ref_draws(unsigned long long seed, unsigned long long offset, const long long* seed_ptr, const long long* offset_ptr,
-                            int variant, long long n_coord, int n_neg, int B,
-                            int cus, int threads_per_cu, float* c1, float* c2, long long* perms, hipStream_t stream);
-unsigned long long ref_draws_advance(long long n_coord, int n_neg, int B, int variant, int cus, int threads_per_cu);
-unsigned long long ref_masks_advance(long long numel, int n_masks, int variant, int cus, int threads_per_cu);
-hipError_t launch_ref_masks(unsigned long long seed, unsigned long long offset, const long long* seed_ptr, const long long* offset_ptr,
-                            int variant, int n_masks, long long numel, float keep_prob, int cus, int threads_per_cu, float* out,
-                            hipStream_t stream);
-size_t dense_workspace_bytes(int B, int C, int M, int N);
-hipError_t launch_dense_corr_panels(const void* imgA, const float* rsA, int imagesA, const void* imgB, const float* rsB, int B, int C, int M, int N,
-                                    float* out, float* rowsum, hipStream_t stream);
-size_t dense_panel_image_bytes(int C, int P);
-hipError_t launch_dense_corr(const MapV& a, const MapV& b, int B, int C, int H1, int W1, int H2, int W2, int normalize,
-                             float* out, void* ws, hipStream_t stream);
-size_t knn_workspace_bytes(long long N, int D, int k, long long q_count);
-hipError_t launch_knn(const float* X, long long N, int D, long long ldx, int k, int normalize, long long q_begin,
-                      long long q_count, long long* out_idx, float* out_val, void* ws, hipStream_t stream);
-hipError_t launch_corr_bwd(const BwdParams& prm, hipStream_t stream);
-}  // namespace stego
+#include "launchers.h"
 
 using namespace stego;
 

@@ -21,6 +21,7 @@
 // Reference: autograd through src/modules.py:335-347, 369-391.
 #include "corr_common.h"
 #include "host_util.h"
+#include "launchers.h"
 
 namespace stego {
 
@@ -1458,45 +1459,10 @@ hipError_t launch_corr_bwd_lists(const BwdParams& prm_in, hipStream_t stream)
     prm.n_build = prm.B < 32 ? prm.B : 32;
     {
         const dim3 grid(prm.n_build + n_tiles);
-#define STEGO_BWDL_CASE(N)                                                                                        \
-    case N: {                                                                                                     \
-        hipError_t ea = ensure_dynamic_lds(reinterpret_cast<const void*>(&corr_bwd_tile_build_kernel<N>), lds);   \
-        if (ea != hipSuccess) return ea;                                                                          \
-        hipLaunchKernelGGL((corr_bwd_tile_build_kernel<N>), grid, dim3(HW_THREADS), lds, stream, prm);            \
-        break;                                                                                                    \
-    }
-#define STEGO_BWDL32_CASE(N)                                                                                      \
-    case N: {                                                                                                     \
-        hipError_t ea = ensure_dynamic_lds(reinterpret_cast<const void*>(&corr_bwd_tile32_build_kernel<N>), lds); \
-        if (ea != hipSuccess) return ea;                                                                          \
-        hipLaunchKernelGGL((corr_bwd_tile32_build_kernel<N>), grid, dim3(NTHREADS), lds, stream, prm);            \
-        break;                                                                                                    \
-    }
-        if (split) {
-            switch (nt) {
-                STEGO_BWDL_CASE(1)
-                STEGO_BWDL_CASE(2)
-                STEGO_BWDL_CASE(3)
-                STEGO_BWDL_CASE(4)
-                STEGO_BWDL_CASE(5)
-                STEGO_BWDL_CASE(6)
-                STEGO_BWDL_CASE(7)
-                default:
-                STEGO_BWDL_CASE(8)
-            }
-        } else {
-            switch (nt) {
-                STEGO_BWDL32_CASE(1)
-                STEGO_BWDL32_CASE(2)
-                STEGO_BWDL32_CASE(3)
-                STEGO_BWDL32_CASE(4)
-                default:
-                STEGO_BWDL32_CASE(5)
-            }
-        }
-#undef STEGO_BWDL_CASE
-#undef STEGO_BWDL32_CASE
-        hipError_t e = hipGetLastError();
+        // channel tiles of 16: the split kernel has 1 .. 8 (anything else: 8), its fp32 twin 1 .. 5 (anything else: 5)
+        const hipError_t e = split
+            ? with_const<1, 2, 3, 4, 5, 6, 7, 8>(nt, [&](auto N) { return launch<corr_bwd_tile_build_kernel<N()>>(grid, dim3(HW_THREADS), lds, stream, prm); })
+            : with_const<1, 2, 3, 4, 5>(nt, [&](auto N) { return launch<corr_bwd_tile32_build_kernel<N()>>(grid, dim3(NTHREADS), lds, stream, prm); });
         if (e != hipSuccess) return e;
     }
     const int upi = prm.H * ((prm.W + 15) >> 4), wpi = (upi + UL_WAVES - 1) / UL_WAVES;
@@ -1521,56 +1487,15 @@ hipError_t launch_corr_bwd(const BwdParams& prm, hipStream_t stream)
         const bool dense = prm.g_intra_cd || prm.g_inter_cd || prm.g_neg_cd || (prm.g_neg_loss && prm.g_neg_loss_stride > 0);
         const int lds = split ? SMH_CT + (4 * 16 * ntg + 2 * TP) * HB_LDR * 2 : SMB_AN + 2 * cside + TP * LDG * 4;
         const dim3 grid(prm.n_sets * prm.B), block(NTHREADS);
-#define STEGO_BWD_CASE(N)                                                                                         \
-    case N: {                                                                                                     \
-        if (split && dense) {                                                                                     \
-            hipError_t ea = ensure_dynamic_lds(reinterpret_cast<const void*>(&corr_bwd_tile_h_kernel<N, true>), lds);   \
-            if (ea != hipSuccess) return ea;                                                                      \
-            hipLaunchKernelGGL((corr_bwd_tile_h_kernel<N, true>), grid, dim3(HW_THREADS), lds, stream, prm);      \
-        } else if (split) {                                                                                       \
-            hipError_t ea = ensure_dynamic_lds(reinterpret_cast<const void*>(&corr_bwd_tile_h_kernel<N, false>), lds);  \
-            if (ea != hipSuccess) return ea;                                                                      \
-            hipLaunchKernelGGL((corr_bwd_tile_h_kernel<N, false>), grid, dim3(HW_THREADS), lds, stream, prm);     \
-        } else {                                                                                                  \
-            hipError_t ea = ensure_dynamic_lds(reinterpret_cast<const void*>(&corr_bwd_tile_kernel<N>), lds);    \
-            if (ea != hipSuccess) return ea;                                                                      \
-            hipLaunchKernelGGL((corr_bwd_tile_kernel<N>), grid, block, lds, stream, prm);                         \
-        }                                                                                                         \
-        break;                                                                                                    \
-    }
         if (nt > 5 && !split) return hipErrorInvalidValue;       // (helper() is limited to K <= 72 by check_desc)
-        if (nt > 5) {
-#define STEGO_BWD_WIDE(N)                                                                                         \
-    case N: {                                                                                                     \
-        if (dense) {                                                                                              \
-            hipError_t ea = ensure_dynamic_lds(reinterpret_cast<const void*>(&corr_bwd_tile_h_kernel<N, true>), lds);   \
-            if (ea != hipSuccess) return ea;                                                                      \
-            hipLaunchKernelGGL((corr_bwd_tile_h_kernel<N, true>), grid, dim3(HW_THREADS), lds, stream, prm);      \
-        } else {                                                                                                  \
-            hipError_t ea = ensure_dynamic_lds(reinterpret_cast<const void*>(&corr_bwd_tile_h_kernel<N, false>), lds);  \
-            if (ea != hipSuccess) return ea;                                                                      \
-            hipLaunchKernelGGL((corr_bwd_tile_h_kernel<N, false>), grid, dim3(HW_THREADS), lds, stream, prm);     \
-        }                                                                                                         \
-        break;                                                                                                    \
-    }
-            switch (nt) {
-                STEGO_BWD_WIDE(6)
-                STEGO_BWD_WIDE(7)
-                default:
-                STEGO_BWD_WIDE(8)
-            }
-#undef STEGO_BWD_WIDE
-        } else
-        switch (nt) {
-            STEGO_BWD_CASE(1)
-            STEGO_BWD_CASE(2)
-            STEGO_BWD_CASE(3)
-            STEGO_BWD_CASE(4)
-            default:
-            STEGO_BWD_CASE(5)
-        }
-#undef STEGO_BWD_CASE
-        hipError_t e = hipGetLastError();
+        // channel tiles of 16: 1 .. 5 (anything else: 5) in either precision; the split kernel alone goes on to 6, 7, 8 (anything beyond: 8)
+        auto tile_h = [&](auto N) {
+            return dense ? launch<corr_bwd_tile_h_kernel<N(), true>>(grid, dim3(HW_THREADS), lds, stream, prm)
+                         : launch<corr_bwd_tile_h_kernel<N(), false>>(grid, dim3(HW_THREADS), lds, stream, prm);
+        };
+        const hipError_t e = nt > 5 ? with_const<6, 7, 8>(nt, tile_h)
+                             : split ? with_const<1, 2, 3, 4, 5>(nt, tile_h)
+                                     : with_const<1, 2, 3, 4, 5>(nt, [&](auto N) { return launch<corr_bwd_tile_kernel<N()>>(grid, block, lds, stream, prm); });
         if (e != hipSuccess) return e;
     }
     // ---- unsample: row-owned register kernel for W <= 64, LDS band kernel beyond
@@ -1598,12 +1523,9 @@ hipError_t launch_corr_bwd(const BwdParams& prm, hipStream_t stream)
         RT = (prm.H + n_bands - 1) / n_bands;                 // even bands
         const int acc_bytes = ((RT * row_bytes + 15) & ~15) + 4 * 64 * 4 + 256;     // band + per-lane dummy cells
         const int lds = acc_bytes + UNS_MAX_CONTRIB * 4 + UNS_MAX_RT * UNS_ROW_CAP * (int)sizeof(UnsRowEntry) + 64;
-        hipError_t ea = ensure_dynamic_lds(reinterpret_cast<const void*>(&corr_unsample_kernel), lds);
-        if (ea != hipSuccess) return ea;
         const dim3 grid(2 * prm.B * n_bands), block(UNS_THREADS);
-        hipLaunchKernelGGL(corr_unsample_kernel, grid, block, lds, stream, prm, RT, n_bands, acc_bytes);
+        return launch<corr_unsample_kernel>(grid, block, lds, stream, prm, RT, n_bands, acc_bytes);
     }
-    return hipGetLastError();
 }
 
 }  // namespace stego

@@ -13,7 +13,7 @@
 // streamed twice, the per-unit bytes go up) - so the launcher takes this kernel only while every item gets a unit of its own.
 //
 // What differs from corr_fused_kernel (everything else - placement by the XCD of the source image, phase 1, the ring, the code chunks,
-// the split-fp16 products, the old_mean rendezvous, the last workgroup's tail - is the same code, included from corr_fused.hip):
+// the split-fp16 products, the old_mean rendezvous, the last workgroup's tail - is the same code, included from corr_fused_kernel.h):
 //   * the grid: n_anchor_wg workgroups in FRONT (dispatched first) that only sample anchors, then 2 x tiles items; the samplers of
 //     XCD x are its anchor workgroups and the workgroups that hold a self-correlation half (no gather stream; the placement puts them
 //     on the first slots of the XCD), all twelve waves, as many passes as the share needs;
@@ -27,8 +27,8 @@
 // Bounded waits: the anchor wait falls back on sampling the anchor itself and the old_mean rendezvous on the last workgroup's repair,
 // as in the full-tile kernel; a PARTNER that does not show up for 20 ms (the device is not ours: the launcher never takes this kernel
 // with STEGO_FLAG_SHARED_DEVICE) poisons the row means - NaN outputs and scalars, counted in the event words - instead of hanging.
-#define STEGO_FUSED_PART 3
-#include "corr_fused.hip"
+#include "corr_fused_kernel.h"
+#include "launchers.h"
 
 namespace stego {
 
@@ -882,20 +882,17 @@ __global__ void __launch_bounds__(64 * NW) corr_fused_half_kernel(const FusedPar
 }
 
 // ------------------------------------------------------------------------------------------------------ launch
-#define STEGO_HALF_ONE(PR, N, NK, NWV)                                                                 \
-    do {                                                                                               \
-        hipError_t e_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&corr_fused_half_kernel<PR, N, NK, NWV>), lds); \
-        if (e_ != hipSuccess) return e_;                                                               \
-        hipLaunchKernelGGL((corr_fused_half_kernel<PR, N, NK, NWV>), grid, dim3(64 * NWV), lds, stream, prm); \
-        return hipSuccess;                                                                             \
-    } while (0)
-#define STEGO_HALF_NK(PR, N, NWV)                                                                      \
-    do {                                                                                               \
-        if (prm.NKC == 1) STEGO_HALF_ONE(PR, N, 1, NWV);                                               \
-        else if (prm.NKC == 2) STEGO_HALF_ONE(PR, N, 2, NWV);                                          \
-        else if (prm.NKC == 3) STEGO_HALF_ONE(PR, N, 3, NWV);                                          \
-        else STEGO_HALF_ONE(PR, N, 4, NWV);                                                            \
-    } while (0)
+// precision and NKC as in launch_fused_nkc (corr_fused_kernel.h): PREC_F32 or else split-fp16; 1, 2, 3 code chunks or else 4
+template <int NJ, int NWV>
+static hipError_t launch_half_nkc(const FusedParams& prm, int precision, dim3 grid, int lds, hipStream_t stream)
+{
+    return with_const<PREC_F32, PREC_F16X3>(precision, [&](auto PR) {
+        return with_const<1, 2, 3, 4>(prm.NKC, [&](auto NK) {
+            return launch<corr_fused_half_kernel<PR(), NJ, NK(), NWV>>(grid, dim3(64 * NWV), lds, stream, prm);
+        });
+    });
+}
+
 // (the caller - launch_corr_fused - has checked half_launch_covers)
 hipError_t launch_fused_half(const FusedParams& prm, int precision, hipStream_t stream)
 {
@@ -904,13 +901,8 @@ hipError_t launch_fused_half(const FusedParams& prm, int precision, hipStream_t 
     const int lds = RING_LDS_BYTES;
     // C = 384: sixteen waves (eight MFMA waves, one row pair per wave in phase 1); C = 768: twelve (its phase 1 holds 96 tap registers);
     // STEGO_DEBUG bit 2: twelve everywhere (same-process A/B)
-    if (prm.C == 384 && !(prm.debug & 2)) {
-        if (precision == PREC_F32) STEGO_HALF_NK(PREC_F32, 3, 16); else STEGO_HALF_NK(PREC_F16X3, 3, 16);
-    }
-    if (precision == PREC_F32) { if (prm.C == 384) STEGO_HALF_NK(PREC_F32, 3, 12); else STEGO_HALF_NK(PREC_F32, 6, 12); }
-    else { if (prm.C == 384) STEGO_HALF_NK(PREC_F16X3, 3, 12); else STEGO_HALF_NK(PREC_F16X3, 6, 12); }
+    if (prm.C == 384 && !(prm.debug & 2)) return launch_half_nkc<3, 16>(prm, precision, grid, lds, stream);
+    return prm.C == 384 ? launch_half_nkc<3, 12>(prm, precision, grid, lds, stream) : launch_half_nkc<6, 12>(prm, precision, grid, lds, stream);
 }
-#undef STEGO_HALF_NK
-#undef STEGO_HALF_ONE
 
 }  // namespace stego

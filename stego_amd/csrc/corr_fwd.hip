@@ -28,6 +28,7 @@
 // Reference path: src/modules.py:275-398.
 #include "corr_tile.h"
 #include "host_util.h"
+#include "launchers.h"
 
 namespace stego {
 
@@ -390,21 +391,11 @@ hipError_t launch_corr_tile(const CorrParams& prm, int precision, hipStream_t st
                ((long long)(prm.H - 1) * m.sh + (long long)(prm.W - 1) * m.sw + prm.C) * 4 < (1ll << 32);
     };
     const bool v4 = ok4(prm.feats) && ok4(prm.feats_pos);
-    const int which = (precision == PREC_F32 ? 0 : 2) + (v4 ? 0 : 1);
-    const void* fns[4] = {reinterpret_cast<const void*>(&corr_tile_kernel<PREC_F32, 4>),
-                          reinterpret_cast<const void*>(&corr_tile_kernel<PREC_F32, 1>),
-                          reinterpret_cast<const void*>(&corr_tile_kernel<PREC_F16X3, 4>),
-                          reinterpret_cast<const void*>(&corr_tile_kernel<PREC_F16X3, 1>)};
-    hipError_t ea = ensure_dynamic_lds(fns[which], lds);
-    if (ea != hipSuccess) return ea;
     const dim3 grid(prm.n_sets * prm.B), block(TILE_THREADS);
-    switch (which) {
-        case 0: hipLaunchKernelGGL((corr_tile_kernel<PREC_F32, 4>), grid, block, lds, stream, prm, stage); break;
-        case 1: hipLaunchKernelGGL((corr_tile_kernel<PREC_F32, 1>), grid, block, lds, stream, prm, stage); break;
-        case 2: hipLaunchKernelGGL((corr_tile_kernel<PREC_F16X3, 4>), grid, block, lds, stream, prm, stage); break;
-        default: hipLaunchKernelGGL((corr_tile_kernel<PREC_F16X3, 1>), grid, block, lds, stream, prm, stage); break;
-    }
-    return hipGetLastError();
+    return with_const<PREC_F32, PREC_F16X3>(precision, [&](auto PR) {       // (PREC_F32 or else the split-fp16 kernel)
+        return v4 ? launch<corr_tile_kernel<PR(), 4>>(grid, block, lds, stream, prm, stage)
+                  : launch<corr_tile_kernel<PR(), 1>>(grid, block, lds, stream, prm, stage);
+    });
 }
 
 // finalize: block 0 writes scalars; the rest fix the loss tensors of the sets that output one

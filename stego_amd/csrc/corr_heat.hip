@@ -498,11 +498,8 @@ extern "C" int stego_corr_heatmaps(const StegoHeatDesc* desc, const StegoMap* sr
     wp.cap_rows = pl.span;
 
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(heat_low_kernel), (int)LOW_LDS_BYTES);
-    if (e != hipSuccess) return hip_rc(e);
     (void)hipGetLastError();
-    heat_low_kernel<<<dim3((unsigned)pl.NCH, (unsigned)pl.NT, (unsigned)desc->B), NTHREADS, LOW_LDS_BYTES, s>>>(lp);
-    e = hipGetLastError();
+    const hipError_t e = launch<heat_low_kernel>(dim3((unsigned)pl.NCH, (unsigned)pl.NT, (unsigned)desc->B), dim3(NTHREADS), (int)LOW_LDS_BYTES, s, lp);
     if (e != hipSuccess) return hip_rc(e);
     const dim3 grid2((unsigned)pl.blocks, (unsigned)desc->N, (unsigned)desc->B);
     if (pl.V == 4)

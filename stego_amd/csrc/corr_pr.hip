@@ -275,9 +275,6 @@ extern "C" int stego_pr_accumulate(const StegoPrDesc* desc, const StegoMap* a, c
     p.flags = desc->flags;
     p.NCH = (desc->C + KC - 1) / KC;
     const dim3 grid((unsigned)((desc->N2 + TP - 1) / TP), (unsigned)((desc->N1 + TP - 1) / TP), (unsigned)desc->B);
-    const hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(corr_pr_kernel), (int)PR_LDS_BYTES);
-    if (e != hipSuccess) return hip_rc(e);
     (void)hipGetLastError();
-    corr_pr_kernel<<<grid, NTHREADS, PR_LDS_BYTES, static_cast<hipStream_t>(stream)>>>(p);
-    return hip_rc(hipGetLastError());
+    return hip_rc(launch<corr_pr_kernel>(grid, dim3(NTHREADS), (int)PR_LDS_BYTES, static_cast<hipStream_t>(stream), p));
 }

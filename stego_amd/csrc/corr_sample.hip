@@ -19,6 +19,8 @@
 // One half-wave (32 lanes) owns one sample point: lane hl holds channels 128*j + 4*hl .. +3, so a
 // wave instruction is two coalesced 512 B runs; the row norm is a 5-step shuffle reduction.
 #include "corr_common.h"
+#include "host_util.h"
+#include "launchers.h"
 
 namespace stego {
 
@@ -268,21 +270,13 @@ hipError_t launch_corr_sample(const SampleParams& prm_in, int precision, hipStre
     prm.div_by = prm.mode == 1 ? prm.W : prm.S;
     prm.div_magic = 65536 / prm.div_by + 1;             // (q * magic) >> 16 == q / div_by for q < 128
     const dim3 grid(prm.n_roles * prm.B * 8), block(NTHREADS);      // 8 units of 16 points per set
-#define STEGO_SAMPLE_LAUNCH(N, PR, CC) hipLaunchKernelGGL((sample_norm_kernel<N, PR, CC>), grid, block, 0, stream, prm)
-#define STEGO_SAMPLE_CASE(N)                                                                        \
-    case N:                                                                                         \
-        if (precision == PREC_F16X3) { if (ccl) STEGO_SAMPLE_LAUNCH(N, PREC_F16X3, true); else STEGO_SAMPLE_LAUNCH(N, PREC_F16X3, false); } \
-        else { if (ccl) STEGO_SAMPLE_LAUNCH(N, PREC_F32, true); else STEGO_SAMPLE_LAUNCH(N, PREC_F32, false); } \
-        break;
-    switch (nj) {
-        STEGO_SAMPLE_CASE(3)
-        STEGO_SAMPLE_CASE(6)
-        default:
-        STEGO_SAMPLE_CASE(0)
-    }
-#undef STEGO_SAMPLE_CASE
-#undef STEGO_SAMPLE_LAUNCH
-    return hipGetLastError();
+    // three or six stages of 128 channels, anything else the generic kernel (0); PREC_F16X3 or else the fp32 kernel
+    return with_const<3, 6, 0>(nj, [&](auto NJ) {
+        return with_const<PREC_F16X3, PREC_F32>(precision, [&](auto PR) {
+            return ccl ? launch<sample_norm_kernel<NJ(), PR(), true>>(grid, block, 0, stream, prm)
+                       : launch<sample_norm_kernel<NJ(), PR(), false>>(grid, block, 0, stream, prm);
+        });
+    });
 }
 
 }  // namespace stego

@@ -32,19 +32,9 @@
 #include "host_util.h"
 #include "../../include/stego_corr.h"
 #include "corr_wide.h"
+#include "launchers.h"
 
 namespace stego {
-
-hipError_t launch_dense_corr_panels_seg(const void* imgA, const float* rsA, int imagesA, const void* imgB, const float* rsB, int B, int C, int M, int N,
-                                        float* out, float* out1, float* out2, int seg, float* rowsum, hipStream_t stream);                     // dense_corr.hip
-size_t dense_panel_image_bytes(int C, int P);
-hipError_t launch_sample_panels2(const StegoMap* map, int C, void* panels, float* row_scale, float* rows_out, float* inv_out,
-                                 const StegoMap* map2, int C2, void* panels2, float* row_scale2, float* rows_out2, float* inv_out2,
-                                 const long long* index, int N, int H, int W, const float* coords, int n_coords, int S, int normalize,
-                                 hipStream_t stream);                                                                                        // sample_sets.hip
-hipError_t launch_sample_scatter(const float* g_rows, const float* rows_n, const float* inv, const StegoMap* d_map, const long long* index, int N, int C,
-                                 int H, int W, const float* coords, int n_coords, int S, const float* extra, int n_extra, long long extra_stride,
-                                 hipStream_t stream);
 
 // ------------------------------------------------------------------------------------------------ forward: the elementwise part
 struct WidePwParams {
@@ -796,12 +786,12 @@ hipError_t launch_wide_bwd(const WideBwdArgs& a, hipStream_t stream)
     const int list_blocks = gather ? 2 * B : 0;
     const int lds_lists = (2 * HW + 1 + nnb + 2 + 512 / 64 + 4) * 4;
     const int lds_tiles = gather && lds_lists > g.tile_bytes ? lds_lists : g.tile_bytes;
-    if ((e = ensure_dynamic_lds(reinterpret_cast<const void*>(&wide_code_tiles_kernel), lds_tiles)) != hipSuccess) return e;
+    if ((e = allow_dynamic_lds<wide_code_tiles_kernel>(lds_tiles)) != hipSuccess) return e;
     p.zero[0] = a.d_code; p.zero[1] = a.d_code_pos;
     p.zero_floats = gather ? 0 : (long long)B * a.H * a.W * K;      // (the gather writes every pixel)
     const int zero_blocks = 2 * (int)((p.zero_floats + WB_ZERO_CHUNK - 1) / WB_ZERO_CHUNK);
     const int lds = 128 * WB_GS * 4 + 2 * g.tile_bytes;
-    if ((e = ensure_dynamic_lds(reinterpret_cast<const void*>(&wide_bwd_kernel), lds)) != hipSuccess) return e;
+    if ((e = allow_dynamic_lds<wide_bwd_kernel>(lds)) != hipSuccess) return e;
     for (int win = 0; win < g.nwin; ++win) {
         // one pass per window of code channels (K <= 88: one): its tiles, then both GEMMs into the window's columns of the row gradients.  The
         // lists / the zeroing ride with the first pass

@@ -422,24 +422,20 @@ Plan plan(const StegoCrfLossDesc* d)
 template <int NT, bool BWD>
 hipError_t launch_pairs_as(const CrfParams& p, unsigned grid, size_t lds, hipStream_t s)
 {
+    constexpr auto kernel = &crf_pairs<NT, BWD>;        // (named once: the attribute and the launch mean the same instantiation)
     if (lds > 64 * 1024) {                              // beyond the default limit of dynamic LDS
-        const hipError_t e = stego::ensure_dynamic_lds(reinterpret_cast<const void*>(&crf_pairs<NT, BWD>), (int)lds);
+        const hipError_t e = stego::allow_dynamic_lds<kernel>((int)lds);
         if (e != hipSuccess) return e;
     }
     (void)hipGetLastError();
-    crf_pairs<NT, BWD><<<grid, PAIR_TPB, lds, s>>>(p);
+    kernel<<<grid, PAIR_TPB, lds, s>>>(p);
     return hipGetLastError();
 }
 
 template <bool BWD>
 hipError_t launch_pairs(int NT, const CrfParams& p, unsigned grid, size_t lds, hipStream_t s)
 {
-    switch (NT) {
-        case 1: return launch_pairs_as<1, BWD>(p, grid, lds, s);
-        case 2: return launch_pairs_as<2, BWD>(p, grid, lds, s);
-        case 3: return launch_pairs_as<3, BWD>(p, grid, lds, s);
-        default: return launch_pairs_as<4, BWD>(p, grid, lds, s);
-    }
+    return stego::with_const<1, 2, 3, 4>(NT, [&](auto N) { return launch_pairs_as<N(), BWD>(p, grid, lds, s); });      // (anything else: 4)
 }
 
 }  // namespace
@@ -520,12 +516,13 @@ extern "C" int stego_crf_loss(const StegoCrfLossDesc* desc, const StegoMap* guid
 
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t lds0 = d_code ? pl.lds[0] : 0;
+    constexpr auto prepare = &crf_prepare;
     if (lds0 > 64 * 1024) {
-        const hipError_t e = stego::ensure_dynamic_lds(reinterpret_cast<const void*>(&crf_prepare), (int)lds0);
+        const hipError_t e = stego::allow_dynamic_lds<prepare>((int)lds0);
         if (e != hipSuccess) return hip_rc(e);
     }
     (void)hipGetLastError();
-    crf_prepare<<<(unsigned)(pl.wgs[0] - (d_code ? 0 : 1)), PREP_TPB, lds0, s>>>(p);
+    prepare<<<(unsigned)(pl.wgs[0] - (d_code ? 0 : 1)), PREP_TPB, lds0, s>>>(p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_rc(e);
     e = d_code ? launch_pairs<true>(pl.NT, p, (unsigned)pl.wgs[1], pl.lds[1], s) : launch_pairs<false>(pl.NT, p, (unsigned)pl.wgs[1], pl.lds[1], s);

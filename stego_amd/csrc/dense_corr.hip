@@ -15,12 +15,9 @@
 //                       instruction writes 128-byte row segments).  Output-write bound at C = 384.
 #include "corr_common.h"
 #include "host_util.h"
+#include "launchers.h"
 
 namespace stego {
-
-hipError_t launch_rowsum(const float* x, float* out, long long rows, int P, hipStream_t stream);          // loss_pointwise.hip
-hipError_t launch_dense_stream(const MapV& a, const MapV& b, int B, int C, int H1, int W1, int H2, int W2, int normalize, float* out, void* ws,
-                               hipStream_t stream);                                                    // dense_stream.hip
 
 constexpr int DC_SIDE = 2 * TP * LDH * 2;          // bytes of one chunk image: hi[128][72] + lo[128][72] fp16
 constexpr int DT_PKS = 68;                         // floats per row of a wave's parked 32 x 64 half quadrant (272 B: conflict-free 16-byte reads along a row)
@@ -711,22 +708,14 @@ hipError_t launch_dense_corr(const MapV& a, const MapV& b, int B, int C, int H1,
         pb.nbA = 0;                                    // the prep kernel's block index then runs over the B blocks only
         hipLaunchKernelGGL(dense_prep_kernel, dim3((unsigned)(B * prm.nbB)), dim3(NTHREADS), 0, stream, pb, vec);
         const int lds2 = DR_NST * DC_SIDE + 512;
-        hipError_t e2 = ensure_dynamic_lds(reinterpret_cast<const void*>(&dense_rowblock_kernel<false>), lds2);
-        if (e2 != hipSuccess) return e2;
-        hipLaunchKernelGGL(dense_rowblock_kernel<false>, dim3((unsigned)(((B + 7) / 8) * 8 * prm.nbA)), dim3(NTHREADS), lds2, stream, prm);
-        return hipGetLastError();
+        return launch<dense_rowblock_kernel<false>>(dim3((unsigned)(((B + 7) / 8) * 8 * prm.nbA)), dim3(NTHREADS), lds2, stream, prm);
     }
     hipLaunchKernelGGL(dense_prep_kernel, dim3((unsigned)(B * (prm.nbA + prm.nbB))), dim3(NTHREADS), 0, stream, prm, vec);
     const int lds = 2 * DC_SIDE;
-    hipError_t ea = ensure_dynamic_lds(reinterpret_cast<const void*>(&dense_tile_kernel), lds);
-    if (ea != hipSuccess) return ea;
-    hipLaunchKernelGGL(dense_tile_kernel, dim3(prm.nbB, prm.nbA, B), dim3(NTHREADS), lds, stream, prm);
-    return hipGetLastError();
+    return launch<dense_tile_kernel>(dim3(prm.nbB, prm.nbA, B), dim3(NTHREADS), lds, stream, prm);
 }
 
 // Both operands already prepared (stego_sample_panels): pair n = A image n % imagesA (M points) x B image n (N points).
-hipError_t launch_dense_corr_panels_seg(const void* imgA, const float* rsA, int imagesA, const void* imgB, const float* rsB, int B, int C, int M, int N,
-                                        float* out, float* out1, float* out2, int seg, float* rowsum, hipStream_t stream);
 hipError_t launch_dense_corr_panels(const void* imgA, const float* rsA, int imagesA, const void* imgB, const float* rsB, int B, int C, int M, int N,
                                     float* out, float* rowsum, hipStream_t stream)
 {
@@ -749,31 +738,19 @@ hipError_t launch_dense_corr_panels_seg(const void* imgA, const float* rsA, int 
     if (prm.NCH <= DR_MAXCH && !(knob(KNOB_DEBUG) & 8192)) {
         if (prm.nbA >= 2 && prm.NCH <= 2 && !(knob(KNOB_DEBUG) & (1 << 20))) {  // (debug bit 20: one row block per workgroup)
             const int ldsp = 2 * DC_SIDE + 1024 + (DR2_THREADS / 64) * 32 * DR_PKS * 4;
-            hipError_t ep = ensure_dynamic_lds(reinterpret_cast<const void*>(&dense_rowpair_kernel<2>), ldsp);
-            if (ep != hipSuccess) return ep;
-            hipLaunchKernelGGL(dense_rowpair_kernel<2>, dim3((unsigned)(((B + 7) / 8) * 8 * ((prm.nbA + 1) / 2))), dim3(DR2_THREADS), ldsp, stream, prm);
-            return hipGetLastError();
+            return launch<dense_rowpair_kernel<2>>(dim3((unsigned)(((B + 7) / 8) * 8 * ((prm.nbA + 1) / 2))), dim3(DR2_THREADS), ldsp, stream, prm);
         }
         const dim3 grid((unsigned)(((B + 7) / 8) * 8 * prm.nbA));
         if (knob(KNOB_DEBUG) & (1 << 19)) {                     // (tools: four ring stages - three copies in flight -, one workgroup per CU)
             const int lds3 = 4 * DC_SIDE + 512;
-            hipError_t e3 = ensure_dynamic_lds(reinterpret_cast<const void*>(&dense_rowblock_kernel<true, 4>), lds3);
-            if (e3 != hipSuccess) return e3;
-            hipLaunchKernelGGL((dense_rowblock_kernel<true, 4>), grid, dim3(NTHREADS), lds3, stream, prm);
-            return hipGetLastError();
+            return launch<dense_rowblock_kernel<true, 4>>(grid, dim3(NTHREADS), lds3, stream, prm);
         }
         const int lds2 = 2 * DC_SIDE + 512;
-        hipError_t e2 = ensure_dynamic_lds(reinterpret_cast<const void*>(&dense_rowblock_kernel<true, 2>), lds2);
-        if (e2 != hipSuccess) return e2;
-        hipLaunchKernelGGL((dense_rowblock_kernel<true, 2>), grid, dim3(NTHREADS), lds2, stream, prm);
-        return hipGetLastError();
+        return launch<dense_rowblock_kernel<true, 2>>(grid, dim3(NTHREADS), lds2, stream, prm);
     }
     if (seg > 0) return hipErrorInvalidValue;                 // (segmented outputs: the row-block kernel only - codes, K <= 384)
     const int lds = 2 * DC_SIDE;
-    hipError_t ea = ensure_dynamic_lds(reinterpret_cast<const void*>(&dense_tile_kernel), lds);
-    if (ea != hipSuccess) return ea;
-    hipLaunchKernelGGL(dense_tile_kernel, dim3(prm.nbB, prm.nbA, B), dim3(NTHREADS), lds, stream, prm);
-    hipError_t e = hipGetLastError();
+    hipError_t e = launch<dense_tile_kernel>(dim3(prm.nbB, prm.nbA, B), dim3(NTHREADS), lds, stream, prm);
     if (e == hipSuccess && rowsum) e = launch_rowsum(out, rowsum, (long long)B * M, N, stream);        // (the tile kernel's workgroups see 128 columns)
     return e;
 }

@@ -24,6 +24,7 @@
 // hide behind the MFMAs: a SIMD has room for ~4 plain / 2 packed VALU instructions per MFMA, tools/ubench/mfma_beside.hip).
 #include "corr_common.h"
 #include "host_util.h"
+#include "launchers.h"
 #include <type_traits>
 
 namespace stego {
@@ -463,22 +464,12 @@ hipError_t launch_dense_stream(const MapV& a, const MapV& b, int B, int C, int H
     hipLaunchKernelGGL(dense_stats_kernel, dim3((unsigned)((rows + 31) / 32)), dim3(NTHREADS), 0, stream, prm);
     const int NCH = (C + KC - 1) / KC;
     const dim3 grid((unsigned)(((B + 7) / 8) * 8 * prm.nbA));
-#define STEGO_DS(N_)                                                                                                    \
-    case N_: {                                                                                                          \
-        hipError_t e_ = ensure_dynamic_lds(reinterpret_cast<const void*>(&dense_stream_kernel<N_>), DS_LDS);            \
-        if (e_ != hipSuccess) return e_;                                                                                \
-        hipLaunchKernelGGL(dense_stream_kernel<N_>, grid, dim3(NTHREADS), DS_LDS, stream, prm);                         \
-        break;                                                                                                          \
-    }
-    switch (NCH) {
+    auto go = [&](auto N) { return launch<dense_stream_kernel<N()>>(grid, dim3(NTHREADS), DS_LDS, stream, prm); };
 #ifndef DS_ONLY6
-        STEGO_DS(2) STEGO_DS(3) STEGO_DS(4) STEGO_DS(5)
+    return with_const_strict<2, 3, 4, 5, 6>(NCH, go);
+#else
+    return with_const_strict<6>(NCH, go);
 #endif
-        STEGO_DS(6)
-        default: return hipErrorInvalidValue;
-    }
-#undef STEGO_DS
-    return hipGetLastError();
 }
 
 }  // namespace stego

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <cmath>
 
+#include "launchers.h"
+
 namespace stego {
 
 struct DrawParams {

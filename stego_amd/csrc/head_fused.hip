@@ -908,11 +908,8 @@ static hipError_t launch_gemm_t(const HeadGemmParams& p, hipStream_t s)
 {
     const int lds_bytes = 2 * (HSIDE + 2 * NW * 8192) + (KVEC ? (EPI == EPI_BIAS ? 2 : 1) * p.n_slot * p.K * (int)sizeof(float) : 0);
     if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
-    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&head_gemm_kernel<KVEC, EPI, NW>), lds_bytes);
-    if (e != hipSuccess) return e;
     const dim3 grid((p.M + HT - 1) / HT, (p.N + HT * NW - 1) / (HT * NW)), block(256 * NW);
-    hipLaunchKernelGGL((head_gemm_kernel<KVEC, EPI, NW>), grid, block, lds_bytes, s, p);
-    return hipGetLastError();
+    return launch<head_gemm_kernel<KVEC, EPI, NW>>(grid, block, lds_bytes, s, p);
 }
 
 static hipError_t launch_gemm(const HeadGemmParams& p, bool kvec, int nw, hipStream_t s)
@@ -1122,13 +1119,10 @@ int stego_head_bwd(const StegoHeadDesc* d, const float* tokens, const float* mas
         if (d->HW >= HKS && (x_tok & 3) == 0 && (x_img & 3) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0 &&
             (reinterpret_cast<uintptr_t>(w.maskX) & 15) == 0) {
             // (HW >= 32: a stage of 32 tokens spans at most two images, which is what the mask selection assumes)
-            if ((er = ensure_dynamic_lds(reinterpret_cast<const void*>(&head_wgrad_tr_kernel), 2 * WG_STAGE)) != hipSuccess) return er;
-            hipLaunchKernelGGL(head_wgrad_tr_kernel, grid, dim3(256), 2 * WG_STAGE, s, w);
+            er = launch<head_wgrad_tr_kernel>(grid, dim3(256), 2 * WG_STAGE, s, w);
         } else {
-            if ((er = ensure_dynamic_lds(reinterpret_cast<const void*>(&head_wgrad_kernel), 4 * HSIDE)) != hipSuccess) return er;
-            hipLaunchKernelGGL(head_wgrad_kernel, grid, dim3(256), 4 * HSIDE, s, w);
+            er = launch<head_wgrad_kernel>(grid, dim3(256), 4 * HSIDE, s, w);
         }
-        er = hipGetLastError();
         if (er != hipSuccess) return er;
         const long long numel = (long long)N * C;
         hipLaunchKernelGGL(head_reduce_kernel, dim3((unsigned)std::max<long long>((numel / 4 + 63) / 64, (N + 255) / 256)), dim3(256), 0, s, part, splits, numel, dW,

@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "../../include/stego_corr.h"
+#include "dispatch.h"
 
 namespace stego {
 
@@ -19,6 +20,26 @@ inline bool aligned(const void* ptr, size_t a) { return (reinterpret_cast<uintpt
 // (device, kernel) pair already has, under a mutex (one process may drive several GPUs from several threads, as the
 // reference's DataParallel feature extraction does, precompute_knns.py:59).
 hipError_t ensure_dynamic_lds(const void* kernel, int bytes);
+
+// One launch of one instantiation: the dynamic-LDS attribute (only when lds > 0), the launch, the runtime's answer to it.  The kernel is
+// named once, as the template argument, so the attribute and the launch cannot mean different instantiations.  (allow_dynamic_lds on its
+// own, where attribute and launch are not one to one: corr_wide.hip sets two kernels' attributes once, in front of a loop of launches;
+// crf_loss.hip and probe_train.hip set theirs only beyond the 64 KB that every kernel may use, and name the kernel once as a constant.)
+template <auto Kernel>
+inline hipError_t allow_dynamic_lds(int lds) { return lds > 0 ? ensure_dynamic_lds(reinterpret_cast<const void*>(Kernel), lds) : hipSuccess; }
+
+template <auto Kernel, class... Args>
+inline hipError_t launch(dim3 grid, dim3 block, int lds, hipStream_t stream, const Args&... args)
+{
+    const hipError_t e = allow_dynamic_lds<Kernel>(lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(Kernel, grid, block, lds, stream, args...);
+    return hipGetLastError();
+}
+
+// with_const (dispatch.h) for launchers that have no instantiation for an unlisted value
+template <int... Vs, class F>
+inline hipError_t with_const_strict(int v, F&& f) { return with_const_or<Vs...>(v, hipErrorInvalidValue, static_cast<F&&>(f)); }
 
 // number of compute units of the current device (cached per device)
 int device_cu_count();

@@ -83,10 +83,7 @@ __global__ void occupy_kernel(long long ticks, int* sink)
 
 hipError_t launch_occupy(int n_wg, int lds_bytes, int micros, hipStream_t stream)
 {
-    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&occupy_kernel), lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(occupy_kernel, dim3(n_wg), dim3(256), lds_bytes, stream, (long long)micros * 100, (int*)nullptr);
-    return hipGetLastError();
+    return launch<occupy_kernel>(dim3(n_wg), dim3(256), lds_bytes, stream, (long long)micros * 100, (int*)nullptr);
 }
 
 // ---- the library's side stream (stego_corr_workspace_prepare_now)

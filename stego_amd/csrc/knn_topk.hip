@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include "corr_common.h"
 #include "host_util.h"
+#include "launchers.h"
 
 namespace stego {
 
@@ -416,12 +417,10 @@ hipError_t launch_knn(const float* X, long long N, int D, long long ldx, int k, 
     hipLaunchKernelGGL(knn_prep_kernel, dim3(prm.nblk), dim3(NTHREADS), 0, stream, prm);
     const bool areg = prm.NCH <= KNN_AREG_CHUNKS;
     const int lds = areg ? (KNN_NST + 1) * KNN_SIDE : 4 * KNN_SIDE;
-    hipError_t ea = ensure_dynamic_lds(areg ? reinterpret_cast<const void*>(&knn_tile_kernel<true>)
-                                            : reinterpret_cast<const void*>(&knn_tile_kernel<false>), lds);
-    if (ea != hipSuccess) return ea;
     const dim3 grid((unsigned)((prm.units_total + prm.units_per_wg - 1) / prm.units_per_wg));
-    if (areg) hipLaunchKernelGGL(knn_tile_kernel<true>, grid, dim3(NTHREADS), lds, stream, prm);
-    else hipLaunchKernelGGL(knn_tile_kernel<false>, grid, dim3(NTHREADS), lds, stream, prm);
+    const hipError_t ea = areg ? launch<knn_tile_kernel<true>>(grid, dim3(NTHREADS), lds, stream, prm)
+                               : launch<knn_tile_kernel<false>>(grid, dim3(NTHREADS), lds, stream, prm);
+    if (ea != hipSuccess) return ea;
     hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)((q_count + NTHREADS / 32 - 1) / (NTHREADS / 32))), dim3(NTHREADS), 0,
                        stream, prm);
     return hipGetLastError();

@@ -9,6 +9,7 @@
 // measured 4.7e-12) and is dropped.  Used by stego_amd.modules.ContrastiveCorrelationLoss.generic_forward.
 #include "corr_common.h"
 #include "host_util.h"
+#include "launchers.h"
 #include "../../include/stego_corr.h"
 
 namespace stego {

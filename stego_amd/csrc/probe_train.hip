@@ -663,12 +663,13 @@ Plan plan(const StegoProbeTrainDesc* d)
 template <int NMAX>
 hipError_t launch_main(const TrainParams& p, unsigned grid, size_t lds, hipStream_t s)
 {
+    constexpr auto kernel = &probe_train_kernel<NMAX>;       // (named once: the attribute and the launch mean the same instantiation)
     if (lds > 64 * 1024) {                       // beyond the default limit of dynamic LDS
-        const hipError_t e = stego::ensure_dynamic_lds(reinterpret_cast<const void*>(&probe_train_kernel<NMAX>), (int)lds);
+        const hipError_t e = stego::allow_dynamic_lds<kernel>((int)lds);
         if (e != hipSuccess) return e;
     }
     (void)hipGetLastError();
-    probe_train_kernel<NMAX><<<grid, TPB, lds, s>>>(p);
+    kernel<<<grid, TPB, lds, s>>>(p);
     return hipGetLastError();
 }
 

@@ -13,6 +13,7 @@
 // stego_amd.modules.ContrastiveCorrelationLoss.generic_forward (cfg.feature_samples > 11, cfg.dim > 128).
 #include "corr_common.h"
 #include "host_util.h"
+#include "launchers.h"
 #include "../../include/stego_corr.h"
 
 namespace stego {
@@ -330,13 +331,10 @@ hipError_t launch_sample_panels2(const StegoMap* map, int C, void* panels, float
     pp.normalize = (normalize ? 1 : 0) | ((knob(KNOB_DEBUG_SAMPLE) & (1 << 16)) ? 2 : 0);
     const int v1 = panel_vw(map, C, rows_out), v2 = map2 ? panel_vw(map2, C2, rows_out2) : -1;
     const dim3 grid((unsigned)(((long long)N * pp.g.P + 3) / 4)), block(256);
-#define STEGO_SP_CASE(A, B) if (v1 == A && v2 == B) hipLaunchKernelGGL((sample_panels_kernel<A, B>), grid, block, 0, stream, pp)
-    STEGO_SP_CASE(4, -1); else STEGO_SP_CASE(2, -1); else STEGO_SP_CASE(0, -1);
-    else STEGO_SP_CASE(4, 4); else STEGO_SP_CASE(4, 2); else STEGO_SP_CASE(4, 0);
-    else STEGO_SP_CASE(2, 4); else STEGO_SP_CASE(2, 2); else STEGO_SP_CASE(2, 0);
-    else STEGO_SP_CASE(0, 4); else STEGO_SP_CASE(0, 2); else STEGO_SP_CASE(0, 0);
-#undef STEGO_SP_CASE
-    return hipGetLastError();
+    // vector widths of the two sides (panel_vw: 4, 2 or 0; -1: no second map)
+    return with_const<4, 2, 0>(v1, [&](auto V1) {
+        return with_const<-1, 4, 2, 0>(v2, [&](auto V2) { return launch<sample_panels_kernel<V1(), V2()>>(grid, block, 0, stream, pp); });
+    });
 }
 
 hipError_t launch_sample_panels(const StegoMap* map, const long long* index, int N, int C, int H, int W, const float* coords, int n_coords, int S,

@@ -807,12 +807,9 @@ int check_desc(const StegoVitDesc* d)
 
 template <int EPI, bool X3> hipError_t launch_gemm_p(const GemmParams& p, hipStream_t stream)
 {
-    hipError_t ea = stego::ensure_dynamic_lds(reinterpret_cast<const void*>(&vit_gemm_kernel<EPI, X3>), GT_LDS);
-    if (ea != hipSuccess) return ea;
     const int mtiles = (p.M + GT_M - 1) / GT_M, ntiles = ntiles192(p.N);
     const int grid = 8 * ((mtiles + 7) / 8) * ntiles;
-    hipLaunchKernelGGL((vit_gemm_kernel<EPI, X3>), dim3(grid), dim3(GT_THREADS), GT_LDS, stream, p, mtiles, ntiles);
-    return hipGetLastError();
+    return stego::launch<vit_gemm_kernel<EPI, X3>>(dim3(grid), dim3(GT_THREADS), GT_LDS, stream, p, mtiles, ntiles);
 }
 
 template <int EPI> hipError_t launch_gemm(const GemmParams& p, bool x3, hipStream_t stream)
