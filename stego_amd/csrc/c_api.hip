@@ -26,7 +26,6 @@ using namespace stego;
 namespace {
 
 bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // largest element offset inside one image must fit in int32 (the kernels use 32-bit tap offsets)
 int to_mapv(const StegoMap* m, int channels, int H, int W, MapV* out)
@@ -69,10 +68,8 @@ struct Geometry {
     int n_roles, nset, NCH, KQ, LDK;
     int NCH2, NKC, kper;            // fused forward: C / 32 feature stages, code K-chunks of kper channels
     size_t rowg_off;
-    size_t stats_bytes, sync_bytes, fs_bytes, csf_bytes, cs_bytes, nrm_bytes, tap_bytes, ctx_bytes, ws_bytes, bwd_ws_bytes;
-    size_t bwd_dt_bytes, bwd_slots_bytes, bwd_pool_bytes;    // lists-first backward: DT rows, list slots, overflow pool (0: not covered)
+    size_t stats_bytes, sync_bytes, fs_bytes, csf_bytes, cs_bytes, nrm_bytes, tap_bytes, ctx_bytes, ws_bytes;
 };
-constexpr size_t BWD_STAMP_BYTES = 65536;    // debug stamps behind the DT rows
 
 Geometry geometry(const StegoCorrDesc* d, bool helper)
 {
@@ -102,19 +99,11 @@ Geometry geometry(const StegoCorrDesc* d, bool helper)
     g.rowg_off = round_up((size_t)d->B * 256 + 2 * n_tiles * 8 * 4, 256);       // column-half launch: 2 x tiles items, 4 granules each, then 128 row-sum granules per item
     g.sync_bytes = g.rowg_off + round_up(2 * n_tiles * (size_t)TP * 8, 256) + 256;   // + 3 more granules per tile: sum lp, sum clamp, applied;   // counters 256 B apart (ANCHOR_CNT_STRIDE); + the done counter
     g.ws_bytes = g.stats_bytes + g.sync_bytes + g.fs_bytes + g.csf_bytes + g.ctx_bytes;
-    g.bwd_dt_bytes = round_up(n_tiles * 2 * TP * g.LDK * sizeof(float), 256);
-    g.bwd_slots_bytes = g.bwd_pool_bytes = 0;
-    if (!helper && d->H <= 64 && d->W <= 64) {
-        // corr_unsample_list_kernel: a 1 KB slot per (image, pixel row, 16-pixel bin) unit of orig_code, a 256-byte slot per unit of
-        // orig_code_pos, and room for every entry (16 bytes, at most 4 per (item, point)) in the overflow pool - an item is one
-        // (tile, side) whose gradient rows land in a destination image
-        const size_t units = (size_t)d->B * d->H * ((d->W + 15) / 16);
-        g.bwd_slots_bytes = round_up(units * (1024 + 256), 256);
-        g.bwd_pool_bytes = round_up((size_t)4 * d->S * d->S * ((size_t)(2 + d->n_neg) * d->B + (size_t)d->n_neg * d->B + d->B) * 16, 256);
-    }
-    g.bwd_ws_bytes = g.bwd_dt_bytes + BWD_STAMP_BYTES + g.bwd_slots_bytes + g.bwd_pool_bytes;
     return g;
 }
+
+// the backward's own geometry, limits and dispatch: corr_bwd_plan.h
+BwdShape bwd_shape(const StegoCorrDesc* d, bool helper) { return BwdShape{d->B, d->K, d->H, d->W, d->S, d->n_neg, helper, d->precision}; }
 
 // feature_samples 12 .. 16: more points than one tile holds - the multi-launch path of corr_wide.hip behind the same entry points
 bool is_wide(const StegoCorrDesc* d) { return d->S * d->S > TP; }
@@ -153,24 +142,24 @@ int fill_bwd_ctx(const StegoCorrDesc* d, bool helper, const void* saved_ctx, voi
                  BwdParams* prm)
 {
     const Geometry g = geometry(d, helper);
+    const BwdShape shape = bwd_shape(d, helper);
+    const BwdWorkspace w = bwd_workspace(shape);
     if (!saved_ctx || !workspace) return STEGO_ERR_NULL;
-    if (workspace_bytes < g.bwd_ws_bytes) return STEGO_ERR_WORKSPACE;
-    if ((size_t)d->W * d->K * 4 > 96 * 1024) return STEGO_ERR_UNSUPPORTED;      // one image row must fit the LDS band
-    if (!helper && (size_t)d->n_neg * d->B + d->n_neg + 2 > 1024) return STEGO_ERR_UNSUPPORTED; // unsample contribution table
+    if (workspace_bytes < w.total) return STEGO_ERR_WORKSPACE;
+    if (const int rc = bwd_check(shape)) return rc;
     const unsigned char* ctx = static_cast<const unsigned char*>(saved_ctx);
     prm->cs = reinterpret_cast<const float*>(ctx);
     prm->nrm = reinterpret_cast<const float*>(ctx + g.cs_bytes);
     prm->tapyx = reinterpret_cast<const int4*>(ctx + g.cs_bytes + g.nrm_bytes);
     prm->tapw = reinterpret_cast<const float4*>(ctx + g.cs_bytes + g.nrm_bytes + g.tap_bytes);
     prm->dt = static_cast<float*>(workspace);
-    if (!helper && g.bwd_pool_bytes && g.bwd_dt_bytes < ((size_t)1 << 32) && g.bwd_pool_bytes < ((size_t)1 << 32) &&
-        g.bwd_slots_bytes < ((size_t)1 << 32)) {
+    if (w.lists) {
         unsigned char* ws = static_cast<unsigned char*>(workspace);
-        prm->uslots = reinterpret_cast<unsigned*>(ws + g.bwd_dt_bytes + BWD_STAMP_BYTES);
-        prm->upool = reinterpret_cast<unsigned*>(ws + g.bwd_dt_bytes + BWD_STAMP_BYTES + g.bwd_slots_bytes);
-        prm->dt_bytes = (unsigned)g.bwd_dt_bytes;
-        prm->uslots_bytes = (unsigned)g.bwd_slots_bytes;
-        prm->upool_bytes = (unsigned)g.bwd_pool_bytes;
+        prm->uslots = reinterpret_cast<unsigned*>(ws + w.slots_off);
+        prm->upool = reinterpret_cast<unsigned*>(ws + w.pool_off);
+        prm->dt_bytes = (unsigned)w.dt_bytes;
+        prm->uslots_bytes = (unsigned)w.slots_bytes;
+        prm->upool_bytes = (unsigned)w.pool_bytes;
     }
     prm->KQ = g.KQ;
     prm->LDK = g.LDK;
@@ -412,13 +401,13 @@ size_t stego_corr_bwd_workspace_bytes(const StegoCorrDesc* desc)
 {
     if (check_desc(desc, false) != STEGO_OK) return 0;
     if (is_wide(desc)) return wide_geom(desc).bwd_ws_bytes;
-    return geometry(desc, false).bwd_ws_bytes;
+    return bwd_workspace(bwd_shape(desc, false)).total;
 }
 
 size_t stego_corr_helper_bwd_workspace_bytes(const StegoCorrDesc* desc)
 {
     if (check_desc(desc, true) != STEGO_OK) return 0;
-    return geometry(desc, true).bwd_ws_bytes;
+    return bwd_workspace(bwd_shape(desc, true)).total;
 }
 
 size_t stego_corr_helper_workspace_bytes(const StegoCorrDesc* desc)

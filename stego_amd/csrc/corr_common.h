@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "corr_consts.h"
+
 namespace stego {
 
 // Workgroup barrier that first drains this wave's LDS-DMA copies.  global_load_lds writes LDS asynchronously and is
@@ -24,14 +26,11 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int TP = 128;        // sample points per side, padded (S*S <= 128)
-constexpr int NTHREADS = 256;  // 4 wave64 (the gather team size everywhere)
+// (TP, NTHREADS, PREC_*: corr_consts.h)
 constexpr int KC = 64;         // channels per staged chunk
 constexpr int LDA = KC + 4;    // f32 stage row stride in floats: 272 B rows, conflict-free ds_read_b128
 constexpr int LDH = KC + 8;    // fp16 stage row stride in elements: 144 B rows, conflict-free ds_read_b128
 constexpr int LDT = 129;       // epilogue tile row stride (odd -> conflict-free column walks)
-
-enum { PREC_F32 = 0, PREC_F16X3 = 1 };
 
 // float32 [N,C,H,W] view; strides in elements. Per-image offsets are < 2^31 (host-checked).
 struct MapV {
@@ -120,7 +119,7 @@ struct BwdParams {
     int B, K, H, W, S, P, n_neg, n_sets;
     int mode;
     int precision;                             // PREC_*: F16X3 = the tile kernel's GEMMs as split-fp16 products (mode 0)
-    int debug;                                 // 1 skip MFMA, 2 skip scatter, 4 / 16 load ablations, 8 stamps, 32 band unsample, 64 / 128 unsample ablations, 512 fp32-MFMA tile kernel, 1024 tile + row kernels instead of lists first
+    int debug;                                 // STEGO_DEBUG_BWD: the bits of enum BwdDebug (corr_bwd_plan.h)
     float cmin, cmax;
 };
 
@@ -213,6 +212,12 @@ __device__ __forceinline__ void tap_for_point(int q, int P, int S, int H, int W,
         const float* c = coords_img + (size_t)(ww * S + hh) * 2;
         make_taps(c[0], c[1], H, W, yx, w);
     }
+}
+
+// rank of this lane among the set bits of a ballot mask
+__device__ __forceinline__ int lane_prefix(unsigned long long mask)
+{
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
 }
 
 template <int V> struct VecT;

@@ -6,6 +6,7 @@
 #include <cstddef>
 
 #include "../../include/stego_corr.h"
+#include "corr_bwd_plan.h"
 #include "corr_common.h"
 
 namespace stego {
@@ -22,8 +23,9 @@ hipError_t prepare_corr_fused(const FusedParams& prm, size_t sync_bytes, hipStre
 hipError_t launch_fused_odd(const FusedParams& prm, int precision, dim3 grid, dim3 block, int lds, hipStream_t stream);
 hipError_t launch_fused_c192(const FusedParams& prm, int precision, dim3 grid, dim3 block, int lds, hipStream_t stream);
 hipError_t launch_fused_half(const FusedParams& prm, int precision, hipStream_t stream);
-// corr_bwd.hip
+// corr_bwd.hip: plans the backward (corr_bwd_plan.h) and launches it; corr_bwd_lists.hip: the launches of a lists-first plan
 hipError_t launch_corr_bwd(const BwdParams& prm, hipStream_t stream);
+hipError_t launch_corr_bwd_lists(const BwdParams& prm, const BwdPlan& plan, hipStream_t stream);
 // draws.hip
 hipError_t launch_fast_draws(const long long* seed, long long n_coord, int n_neg, int B, float* c1, float* c2, long long* perms,
                              hipStream_t stream);

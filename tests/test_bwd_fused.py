@@ -1,5 +1,5 @@
 """The lists-first backward (corr_bwd_tile_build_kernel: builders beside the tiles; corr_unsample_list_kernel: one wave per
-destination unit, csrc/corr_bwd.hip) against the fp64 oracle's autograd restatement (reference: autograd through
+destination unit, csrc/corr_bwd_lists.hip) against the fp64 oracle's autograd restatement (reference: autograd through
 src/modules.py:325-347, 369-391) and against the tile + row kernels it replaces, through the C ABI.  Needs the MI355X."""
 import os
 
@@ -94,6 +94,8 @@ def test_cfg2_full_size_lists_first_equals_the_row_kernel_and_is_repeatable():
     (2, 384, 12, 12, 100, 6, 2),     # K = 100: seven channel tiles, two operand groups in the tile role
     (5, 32, 16, 16, 70, 11, 5),      # S = 11 on a small map: long lists per unit (more than one step of 64 entries)
     (40, 32, 8, 8, 24, 5, 5),        # more builders' images than builder workgroups (32)
+    (2, 32, 65, 16, 8, 5, 1),        # one row past the lists' map: no slots in the workspace, the row kernel either way
+    (2, 32, 16, 65, 8, 5, 1),        # one column past it: the band kernel either way
 ])
 def test_lists_first_backward_edge_shapes_against_the_oracle(shape):
     B, C, H, W, K, S, n_neg = shape

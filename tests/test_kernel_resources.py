@@ -99,22 +99,31 @@ def test_backward_kernels_do_not_spill(tmp_path):
     """Every kernel of the loss backward (tiles with and without builders in both precisions, the list and the row unsample) keeps its
     working set in registers today; the training pair - corr_bwd_tile_build_kernel<5> (K = 70) and corr_unsample_list_kernel<1, 1> - at the
     occupancies the workgroup sizes of the launch need."""
-    src = os.path.join(ROOT, "stego_amd", "csrc", "corr_bwd.hip")
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", os.path.join(ROOT, "stego_amd", "csrc"),
-           "-I", os.path.join(ROOT, "include"), "-c", src, "-o", str(tmp_path / "bwd.o"), "-Rpass-analysis=kernel-resource-usage"]
-    res = subprocess.run(cmd, capture_output=True, text=True, cwd=str(tmp_path))
-    assert res.returncode == 0, res.stderr[-2000:]
-    kernels, name = {}, None
-    for line in res.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs Spill|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and name:
-            kernels[name][m.group(1)] = int(m.group(2))
-    assert len(kernels) >= 40, sorted(kernels)
+    from concurrent.futures import ThreadPoolExecutor
+
+    def compile_one(name):       # the general path + dispatch, and the training path (lists first)
+        src = os.path.join(ROOT, "stego_amd", "csrc", name)
+        cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", os.path.join(ROOT, "stego_amd", "csrc"),
+               "-I", os.path.join(ROOT, "include"), "-c", src, "-o", str(tmp_path / (name + ".o")), "-Rpass-analysis=kernel-resource-usage"]
+        return subprocess.run(cmd, capture_output=True, text=True, cwd=str(tmp_path))
+
+    with ThreadPoolExecutor(2) as ex:
+        results = list(ex.map(compile_one, ["corr_bwd.hip", "corr_bwd_lists.hip"]))
+    kernels = {}
+    for res in results:
+        assert res.returncode == 0, res.stderr[-2000:]
+        name = None
+        for line in res.stderr.splitlines():
+            m = re.search(r"Function Name: (\S+)", line)
+            if m:
+                name = m.group(1)
+                assert name not in kernels, name          # every kernel lives in one unit
+                kernels[name] = {}
+                continue
+            m = re.search(r"remark:\s+(VGPRs Spill|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
+            if m and name:
+                kernels[name][m.group(1)] = int(m.group(2))
+    assert len(kernels) == 42, sorted(kernels)
     for k, v in kernels.items():
         assert v["VGPRs Spill"] == 0 and v["ScratchSize [bytes/lane]"] == 0, (k, v)
     assert kernels["_ZN5stego26corr_bwd_tile_build_kernelILi5EEEvNS_9BwdParamsE"]["Occupancy [waves/SIMD]"] >= 2        # 512 threads: one workgroup per CU
