@@ -98,6 +98,10 @@ enum {
  * helper()); 128 < S*S <= 256 (S = 12 .. 16, ABI 7): K <= 128, any C and layout - the same entry points run the multi-launch kernels of
  * csrc/corr_wide.hip (stego_corr_fwd_launches says 8; split-fp16 products in both precision modes; bitwise repeatable like S <= 11 unless a
  * pixel of a map receives more than 64 sample taps or the map has more than 4096 pixels); every per-image element offset < 2^31.
+ * The backward (stego_corr_bwd, S*S <= 128) has two limits of its own (csrc/corr_bwd_plan.h, bwd_check): one map row of codes fits the 96 KB
+ * LDS band of its unsample, W * K * 4 <= 98304 bytes (W <= 192 at K = 128), and at most 1024 gradient matrices can land in one image,
+ * 2 + n_neg + n_neg * B <= 1024 (B <= 203 at n_neg = 5); the forward takes such a descriptor, the backward returns STEGO_ERR_UNSUPPORTED
+ * before it launches anything.
  * Anything else returns STEGO_ERR_UNSUPPORTED.  For K > 80 the backward's
  * GEMMs are split-fp16 products in both precision modes (their fp32 operand images no longer fit LDS).
  * Determinism: every kernel sums in a fixed order (bitwise repeatable results), with ONE exception: the backward of maps

@@ -320,7 +320,7 @@ const char* stego_error_string(int code)
         case STEGO_OK: return "ok";
         case STEGO_ERR_NULL: return "required pointer is NULL";
         case STEGO_ERR_SHAPE: return "bad or inconsistent dimension";
-        case STEGO_ERR_UNSUPPORTED: return "unsupported configuration (limits: S<=16, K<=128 (K>72: channels-last maps with C = 192 / 384 / 768, B <= compute units), n_neg<=254, fp32 maps, <2^31 elements per image, no unknown flags)";
+        case STEGO_ERR_UNSUPPORTED: return "unsupported configuration (limits: S<=16, K<=128 (K>72: channels-last maps with C = 192 / 384 / 768, B <= compute units), n_neg<=254, fp32 maps, <2^31 elements per image, no unknown flags; backward: W*K*4<=98304, 2+n_neg+n_neg*B<=1024)";
         case STEGO_ERR_WORKSPACE: return "workspace too small";
         case STEGO_ERR_ALIGN: return "pointer not 4-byte aligned";
         case STEGO_ERR_CRF_LIMITS: return "dense CRF limits: 1 <= C <= 64 labels, H * W * 6 < 2^31 (include/stego_crf.h)";

@@ -764,6 +764,9 @@ class _HelperFunction(torch.autograd.Function):
 
 # --------------------------------------------------------------------------- the loss
 _PAIR_SET_BOUND = {}
+# the backward's own limits (csrc/corr_bwd_plan.h: UNS_BAND_BYTES, UNS_MAX_CONTRIB; include/stego_corr.h "Limits of this build")
+_BWD_BAND_BYTES = 96 * 1024
+_BWD_MAX_CONTRIB = 1024
 
 
 def _pair_set_bound(device=None):
@@ -821,17 +824,20 @@ class ContrastiveCorrelationLoss(nn.Module):
         return coords1, coords2
 
     @staticmethod
-    def fused_kernels_cover(B, C, K, H, W, S, device=None):
+    def fused_kernels_cover(B, C, K, H, W, S, device=None, n_neg=0):
         """Does the hand-written loss path (stego_corr_fwd / _bwd, include/stego_corr.h "Limits of this build") take this shape?
         S * S <= 128 sample points per image: K <= 72 on any layout, 72 < K <= 128 on the single-launch forward (any parity, ViT widths, B and the
-        map within its bounds); 128 < S * S <= 256 (cfg.feature_samples 12 .. 16): any K <= 128, any layout.  Everything else is computed by
-        generic_forward()."""
+        map within its bounds), and what the backward's unsample holds (csrc/corr_bwd_plan.h, bwd_check): one map row of W * K floats in its 96 KB
+        LDS band, 2 + n_neg + n_neg * B <= 1024 gradient matrices that can land in one image; 128 < S * S <= 256 (cfg.feature_samples 12 .. 16):
+        any K <= 128, any layout.  Everything else is computed by generic_forward()."""
         if K > 128 or H > 32767 or W > 32767:
             return False
         if S * S > 128:
             # 129 .. 256 points per image (cfg.feature_samples 12 .. 16): the multi-launch kernels of csrc/corr_wide.hip behind the same entry
-            # points (round 5)
+            # points (round 5), with a backward of their own
             return S <= 16 and (2 + 253) * B <= 65535
+        if W * K * 4 > _BWD_BAND_BYTES or 2 + n_neg + n_neg * B > _BWD_MAX_CONTRIB:
+            return False            # stego_corr_fwd would take it, stego_corr_bwd then refuse it
         if K > 72:
             return C in (192, 384, 768) and B <= _pair_set_bound(device) and H <= 256 and W <= 256
         return True
@@ -935,9 +941,9 @@ class ContrastiveCorrelationLoss(nn.Module):
         B, C, H, W = orig_feats.shape
         K = orig_code.shape[1]
         S = cfg.feature_samples
-        if orig_feats.is_cuda and not self.fused_kernels_cover(B, C, K, H, W, S, orig_feats.device):
-            return self.generic_forward(orig_feats, orig_feats_pos, orig_code, orig_code_pos, coords1, coords2, perms)
         n_neg = int(perms.shape[0]) if perms is not None else 0
+        if orig_feats.is_cuda and not self.fused_kernels_cover(B, C, K, H, W, S, orig_feats.device, n_neg):
+            return self.generic_forward(orig_feats, orig_feats_pos, orig_code, orig_code_pos, coords1, coords2, perms)
         if perms is None:
             perms = torch.zeros(0, B, dtype=torch.long, device=orig_feats.device)
         desc = capi.make_desc(B, C, K, H, W, S, n_neg, cfg,
@@ -975,11 +981,11 @@ class ContrastiveCorrelationLoss(nn.Module):
         coords1, coords2, perms = self.draw(orig_feats, orig_salience, orig_salience_pos)
         cfg = self.cfg
         B, C, H, W = orig_feats.shape
-        if orig_feats.is_cuda and not self.fused_kernels_cover(B, C, orig_code.shape[1], H, W, cfg.feature_samples, orig_feats.device):
+        n_neg = int(perms.shape[0]) if perms is not None else 0
+        if orig_feats.is_cuda and not self.fused_kernels_cover(B, C, orig_code.shape[1], H, W, cfg.feature_samples, orig_feats.device, n_neg):
             o = self.generic_forward(orig_feats, orig_feats_pos, orig_code, orig_code_pos, coords1, coords2, perms)
             neg_mean = o[4].mean() if o[4].numel() else o[0].new_zeros(())
             return torch.stack([o[0], o[2], neg_mean]), o[1], o[3], o[5]
-        n_neg = int(perms.shape[0]) if perms is not None else 0
         if perms is None:
             perms = torch.zeros(0, B, dtype=torch.long, device=orig_feats.device)
         desc = capi.make_desc(B, C, orig_code.shape[1], H, W, cfg.feature_samples, n_neg, cfg,
