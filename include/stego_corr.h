@@ -32,7 +32,9 @@ extern "C" {
                                 * 4: StegoHeadDesc.tokens_amax, stego_tokens_from_cache, stego_ref_dropout_masks, stego_ref_draws_indirect, stego_corr_workspace_prepare_now
                                 * 5: stego_corr_event_counters
                                 * 6: StegoVitDesc.precision (STEGO_VIT_F16X3: the backbone in the fp32 class)
-                                * 7: stego_sample, stego_sample_bwd, stego_rowsum, stego_loss_pointwise_fwd / _bwd, stego_sample_panels, stego_dense_corr_panels, stego_sample_bwd_rows; stego_corr_fwd / _bwd take S = 12 .. 16 */
+                                * 7: stego_sample, stego_sample_bwd, stego_rowsum, stego_loss_pointwise_fwd / _bwd, stego_sample_panels, stego_dense_corr_panels, stego_sample_bwd_rows; stego_corr_fwd / _bwd take S = 12 .. 16
+                                *    (entry points added since, here stego_dense_corr_kernel, and the other headers' are additions: no existing
+                                *    signature or struct changed, the number stays) */
 
 enum {
     STEGO_OK = 0,
@@ -54,6 +56,11 @@ enum {
                              /* every forward path; in the single-launch forward also the code correlation, and    */
                              /* in the backward the two code GEMMs (the three-launch forward keeps the code        */
                              /* correlation in exact fp32)                                                         */
+                             /* LIMIT (S <= 11): the prescale of a sampled point is taken from the FIRST stage (32  */
+                             /* feature channels, one code K-chunk) in which the point is non-zero - any stage -    */
+                             /* and later stages are staged with it: their channels may be up to 2^15 times that    */
+                             /* stage's largest (tested at 2^14); beyond, fp16 overflows and outputs are not        */
+                             /* finite.  STEGO_PREC_F32 has no such limit (tested at 2^20), nor has S >= 12.        */
 };
 
 /* hipStream_t without dragging the HIP headers into C callers. */
@@ -342,6 +349,20 @@ size_t stego_dense_corr_workspace_bytes(int32_t B, int32_t C, int32_t H1, int32_
 int stego_dense_corr(const StegoMap* a, const StegoMap* b, int32_t B, int32_t C, int32_t H1, int32_t W1, int32_t H2,
                      int32_t W2, int32_t normalize, float* out, void* workspace, size_t workspace_bytes,
                      stego_stream_t stream);
+
+/* Which kernel stego_dense_corr would launch for these maps: the argument checks of stego_dense_corr (dimensions, map pointers and
+ * strides), then host arithmetic on strides and dimensions only - no map data is read, no HIP call is made, so it can be asked
+ * anywhere.  Returns a STEGO_DENSE_* value, or the NEGATIVE of the error code stego_dense_corr would return (-STEGO_ERR_UNSUPPORTED
+ * also where none of the kernels is correct for the call: an image x block grid beyond 2^31 - 1, or maps only the tile kernel takes
+ * with H1 * W1 > 65535 * 128).  The stream kernel forms 32-bit byte offsets: it is taken only while an image's output is at most
+ * 2^32 bytes (H1 * W1 * H2 * W2 <= 2^30) and (H2 * W2 - 1) * 4 * b.stride_w + 4 * C <= 2^32; beyond either the same maps go to the
+ * row-block kernel, whose addresses are 64-bit. */
+enum {
+    STEGO_DENSE_STREAM = 0,    /* csrc/dense_stream.hip: channels-last maps, 64 < C <= 384, C % 8 == 0, b's pixels at a dense stride */
+    STEGO_DENSE_ROWBLOCK = 1,  /* csrc/dense_corr.hip, dense_rowblock_kernel: channels-last maps, C <= 384, C % 8 == 0                */
+    STEGO_DENSE_TILE = 2       /* csrc/dense_corr.hip, dense_tile_kernel: every other layout and width                              */
+};
+int stego_dense_corr_kernel(const StegoMap* a, const StegoMap* b, int32_t B, int32_t C, int32_t H1, int32_t W1, int32_t H2, int32_t W2);
 
 /* ---- sample() with an image index (reference: sample(), src/modules.py:287-288, as ContrastiveCorrelationLoss.forward calls it on
  * orig_feats[perm] / orig_code[perm], :384-385 - without the permuted copy of the maps).

@@ -254,6 +254,7 @@ SIGNATURES = {
     "stego_corr_helper_saved_ctx_bytes": (c_size_t, [_D]),
     "stego_dense_corr_workspace_bytes": (c_size_t, [c_int32] * 6),
     "stego_dense_corr": (c_int32, [_M, _M] + [c_int32] * 7 + [_P, _P, c_size_t, _P]),
+    "stego_dense_corr_kernel": (c_int32, [_M, _M] + [c_int32] * 6),
     "stego_sample": (c_int32, [_M, _P, c_int32, c_int32, c_int32, c_int32, _P, c_int32, c_int32, _P, _P]),
     "stego_sample_bwd": (c_int32, [_P, _M, _P, c_int32, c_int32, c_int32, c_int32, _P, c_int32, c_int32, _P]),
     "stego_sample_bwd_rows": (c_int32, [_P, _P, _P, _M, _P, c_int32, c_int32, c_int32, c_int32, _P, c_int32, c_int32, _P]),
@@ -791,6 +792,23 @@ def dense_corr(a, b, normalize=False):
         _check(lib.stego_dense_corr(byref(ma), byref(mb), B, C, H1, W1, H2, W2, 1 if normalize else 0, _ptr(out), _ptr(ws),
                                     ws.numel(), _stream()))
     return out
+
+
+DENSE_KERNELS = ("stream", "rowblock", "tile")      # STEGO_DENSE_* of include/stego_corr.h
+
+
+def dense_corr_kernel(a, b):
+    """The kernel dense_corr(a, b) would launch - "stream", "rowblock" or "tile" (stego_dense_corr_kernel: strides and shapes only,
+    nothing is launched and no map data is read, so host tensors are taken as well)."""
+    if a.dim() != 4 or b.dim() != 4 or a.shape[:2] != b.shape[:2]:
+        raise ValueError("dense_corr_kernel expects two 4-D maps of one batch size and width")
+    B, C, H1, W1 = a.shape
+    H2, W2 = b.shape[2:]
+    ma, mb = _map(a), _map(b)
+    rc = load().stego_dense_corr_kernel(byref(ma), byref(mb), B, C, H1, W1, H2, W2)
+    if rc < 0:
+        _check(-rc)
+    return DENSE_KERNELS[rc]
 
 
 def sample(t, coords, index=None):

@@ -320,7 +320,7 @@ const char* stego_error_string(int code)
         case STEGO_OK: return "ok";
         case STEGO_ERR_NULL: return "required pointer is NULL";
         case STEGO_ERR_SHAPE: return "bad or inconsistent dimension";
-        case STEGO_ERR_UNSUPPORTED: return "unsupported configuration (limits: S<=16, K<=128 (K>72: channels-last maps with C = 192 / 384 / 768, B <= compute units), n_neg<=254, fp32 maps, <2^31 elements per image, no unknown flags; backward: W*K*4<=98304, 2+n_neg+n_neg*B<=1024)";
+        case STEGO_ERR_UNSUPPORTED: return "unsupported configuration (limits: S<=16, K<=128 (K>72: channels-last maps with C = 192 / 384 / 768, B <= compute units), n_neg<=254, fp32 maps, <2^31 elements per image, no unknown flags; backward: W*K*4<=98304, 2+n_neg+n_neg*B<=1024; dense correlation: H*W<=2^24 per map, B<=65535, B*(128-pixel blocks of a map)<2^31, H1*W1<=65535*128 unless both maps are channels-last with C%8==0, C<=384)";
         case STEGO_ERR_WORKSPACE: return "workspace too small";
         case STEGO_ERR_ALIGN: return "pointer not 4-byte aligned";
         case STEGO_ERR_CRF_LIMITS: return "dense CRF limits: 1 <= C <= 64 labels, H * W * 6 < 2^31 (include/stego_crf.h)";
@@ -755,6 +755,17 @@ size_t stego_dense_corr_workspace_bytes(int32_t B, int32_t C, int32_t H1, int32_
     return dense_workspace_bytes(B, C, H1 * W1, H2 * W2);
 }
 
+int stego_dense_corr_kernel(const StegoMap* a, const StegoMap* b, int32_t B, int32_t C, int32_t H1, int32_t W1, int32_t H2, int32_t W2)
+{
+    int rc = dense_check(B, C, H1, W1, H2, W2);
+    if (rc) return -rc;
+    MapV ma, mb;
+    if ((rc = to_mapv(a, C, H1, W1, &ma))) return -rc;
+    if ((rc = to_mapv(b, C, H2, W2, &mb))) return -rc;
+    const int kernel = dense_corr_kernel(ma, mb, B, C, H1, W1, H2, W2, knob(KNOB_DEBUG));
+    return kernel < 0 ? -STEGO_ERR_UNSUPPORTED : kernel;
+}
+
 int stego_dense_corr(const StegoMap* a, const StegoMap* b, int32_t B, int32_t C, int32_t H1, int32_t W1, int32_t H2,
                      int32_t W2, int32_t normalize, float* out, void* workspace, size_t workspace_bytes,
                      stego_stream_t stream)
@@ -767,6 +778,7 @@ int stego_dense_corr(const StegoMap* a, const StegoMap* b, int32_t B, int32_t C,
     MapV ma, mb;
     if ((rc = to_mapv(a, C, H1, W1, &ma))) return rc;
     if ((rc = to_mapv(b, C, H2, W2, &mb))) return rc;
+    if (dense_corr_kernel(ma, mb, B, C, H1, W1, H2, W2, knob(KNOB_DEBUG)) < 0) return STEGO_ERR_UNSUPPORTED;
     return hip_rc(launch_dense_corr(ma, mb, B, C, H1, W1, H2, W2, normalize ? 1 : 0, out, workspace,
                                     static_cast<hipStream_t>(stream)));
 }

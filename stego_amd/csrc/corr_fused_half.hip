@@ -516,7 +516,8 @@ __global__ void __launch_bounds__(64 * NW) corr_fused_half_kernel(const FusedPar
         const int g8 = gt & 7, prow = gt >> 3;       // prow = my point inside the half, q0 + prow inside the set
         const int gwave = wave;
         const int q = q0 + prow;
-        float ss = 0.f, bsc = 0.f, ssc = 0.f, bscc = 0.f;
+        float ss = 0.f, ssc = 0.f;
+        float bsc = q < P ? 0.f : 1.f, bscc = bsc;   // prescales: 0 = undecided; the padding behind the set's points (all zeros) never decides
         if (lane < 8) {
             const int ql = 8 * gwave + lane, qq = q0 + ql;
             const f32x2 cxy = *reinterpret_cast<const f32x2*>(coordsB + coord_index(prm, qq));
@@ -568,7 +569,8 @@ __global__ void __launch_bounds__(64 * NW) corr_fused_half_kernel(const FusedPar
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = tw.x * g.tv[0][e] + tw.y * g.tv[1][e] + tw.z * g.tv[2][e] + tw.w * g.tv[3][e];
         };
-        auto commit_feat = [&](const HSet& g, int m, bool decide) {
+        // (the prescale: from the first stage in which the point is non-zero, whichever it is - see corr_fused_kernel.h)
+        auto commit_feat = [&](const HSet& g, int m) {
             unsigned char* dst = ring + (m & (RS_NS - 1)) * RS_STAGE + RS_SIDE;
             float v[4];
             blend(g, v);
@@ -576,7 +578,7 @@ __global__ void __launch_bounds__(64 * NW) corr_fused_half_kernel(const FusedPar
             if constexpr (PREC == PREC_F32) {
                 *reinterpret_cast<f32x4*>(dst + swz_f(prow, g8)) = f32x4{v[0], v[1], v[2], v[3]};
             } else {
-                if (decide && bsc == 0.f) {
+                if (bsc == 0.f) {
                     float mx = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
 #pragma unroll
                     for (int mm = 4; mm >= 1; mm >>= 1) mx = fmaxf(mx, __shfl_xor(mx, mm, 64));
@@ -604,9 +606,9 @@ __global__ void __launch_bounds__(64 * NW) corr_fused_half_kernel(const FusedPar
             if constexpr (!CH) {
                 *reinterpret_cast<f32x4*>(dst + swz_f(prow, g8)) = cv[m];
             } else {
-                // format H, as a feature stage: a power-of-two prescale per point from the first chunk in which it is non-zero among the
-                // first two, fp16 hi / lo split, one 16-byte store per lane (lanes beyond kper / 4 hold zeros: the stage's padding)
-                if (m < 2 && bscc == 0.f) {
+                // format H, as a feature stage: a power-of-two prescale per point from the first chunk in which it is non-zero (any of
+                // the NKC), fp16 hi / lo split, one 16-byte store per lane (lanes beyond kper / 4 hold zeros: the stage's padding)
+                if (bscc == 0.f) {
                     float mx = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
 #pragma unroll
                     for (int mm = 4; mm >= 1; mm >>= 1) mx = fmaxf(mx, __shfl_xor(mx, mm, 64));
@@ -647,7 +649,7 @@ __global__ void __launch_bounds__(64 * NW) corr_fused_half_kernel(const FusedPar
         };
         auto commit = [&](HSet& g, int m) {
             if (m < NKC) { commit_code(g, m); if (m == NKC - 1) finish_codes(); }
-            else commit_feat(g, m, m - NKC < 2);
+            else commit_feat(g, m);
         };
         static_assert(NT >= 8, "the static head covers the code chunks and the first feature stages");
         {
@@ -673,18 +675,18 @@ __global__ void __launch_bounds__(64 * NW) corr_fused_half_kernel(const FusedPar
 #pragma unroll 1
         for (int n = 4; n < TAIL0; n += 2) {
             ring_barrier();                          // B(n)
-            commit_feat(ga, n + 2, false);
+            commit_feat(ga, n + 2);
             __builtin_amdgcn_sched_barrier(0);
             issue_feat(ga, n + 4 - NKC);
             ring_barrier();                          // B(n + 1)
-            commit_feat(gb, n + 3, false);
+            commit_feat(gb, n + 3);
             __builtin_amdgcn_sched_barrier(0);
             issue_feat(gb, n + 5 - NKC);
         }
 #pragma unroll
         for (int n = TAIL0; n < NT; ++n) {
             ring_barrier();                          // B(n)
-            if (n + 2 < NT) { if (n & 1) commit_feat(gb, n + 2, false); else commit_feat(ga, n + 2, false); }
+            if (n + 2 < NT) { if (n & 1) commit_feat(gb, n + 2); else commit_feat(ga, n + 2); }
             if (n + 4 < NT) { if (n & 1) issue_feat(gb, n + 4 - NKC); else issue_feat(ga, n + 4 - NKC); }
         }
         {

@@ -1130,7 +1130,10 @@ __global__ void __launch_bounds__(FUSED_THREADS) corr_fused_kernel(const FusedPa
         const int gwave = wave8 - 4;
         float ss[GI], bsc[GI], ssc[GI], bscc[GI];
 #pragma unroll
-        for (int j = 0; j < GI; ++j) { ss[j] = 0.f; bsc[j] = 0.f; ssc[j] = 0.f; bscc[j] = 0.f; }
+        for (int j = 0; j < GI; ++j) {
+            ss[j] = 0.f; ssc[j] = 0.f;
+            bsc[j] = bscc[j] = GP * j + prow < P ? 0.f : 1.f;       // prescales: 0 = undecided; the padding behind the set's points (all zeros) never decides
+        }
         if (lane < 8 * GI) {
             // tap table of the B points: every wave computes the 8 GI entries it reads itself (no barrier needed)
             const int q = GP * (lane >> 3) + 8 * gwave + (lane & 7);
@@ -1223,10 +1226,12 @@ __global__ void __launch_bounds__(FUSED_THREADS) corr_fused_kernel(const FusedPa
             for (int e = 0; e < 4; ++e) v[e] = w.x * g.tv[j][0][e] + w.y * g.tv[j][1][e] + w.z * g.tv[j][2][e] + w.w * g.tv[j][3][e];
         };
         // Commit FEATURE stage m (m >= NKC) to the B side of its ring slot (raw samples; 1/||b|| becomes a column scale).
-        // decide: the point's power-of-two prescale is chosen from the first feature stage in which it is non-zero
-        // among the first two (|x| * bsc in [0.5, 1)); later stages are branch-free (F.normalize is scale invariant, the
-        // column scale divides the prescale out again; fp16 leaves 2^15 of headroom for channels beyond those stages).
-        auto commit_feat = [&](const GSet& g, int m, bool decide) {
+        // The point's power-of-two prescale is chosen from the first feature stage in which it is non-zero, whichever stage
+        // that is (|x| * bsc in [0.5, 1) there; as corr_tile.h: an undecided point costs every stage one compare, uniform over the
+        // point's lanes).  F.normalize is scale invariant, the column scale divides the prescale out again.  Stages behind
+        // the deciding one are staged with its scale: fp16 leaves them 2^15 of headroom (the limit of STEGO_PREC_F16X3 in
+        // include/stego_corr.h; tests/test_parity_gpu.py holds the inside edge, channels 2^14 above the deciding stage).
+        auto commit_feat = [&](const GSet& g, int m) {
             unsigned char* dst = ring + (m & (RS_NS - 1)) * RS_STAGE + RS_SIDE;
 #pragma unroll
             for (int j = 0; j < GI; ++j) {
@@ -1237,7 +1242,7 @@ __global__ void __launch_bounds__(FUSED_THREADS) corr_fused_kernel(const FusedPa
                 if constexpr (PREC == PREC_F32) {
                     *reinterpret_cast<f32x4*>(dst + swz_f(q, g8)) = f32x4{v[0], v[1], v[2], v[3]};
                 } else {
-                    if (decide && bsc[j] == 0.f) {
+                    if (bsc[j] == 0.f) {                     // (uniform over the lanes of a point)
                         float mx = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
 #pragma unroll
                         for (int mm = 4; mm >= 1; mm >>= 1) mx = fmaxf(mx, __shfl_xor(mx, mm, 64));
@@ -1260,7 +1265,7 @@ __global__ void __launch_bounds__(FUSED_THREADS) corr_fused_kernel(const FusedPa
         };
         // commit a CODE stage m: raw fp32 samples to the B side of its ring slot
         // F16X3: the MFMA team splits these operands into fp16 halves, so the raw samples get a power-of-two prescale per point,
-        // chosen from the first code stage in which the point is non-zero among the first two (as for the features)
+        // chosen from the first code stage in which the point is non-zero, whichever chunk that is (as for the features)
         auto commit_code = [&](const GSet& g, int m) {
             unsigned char* dst = ring + (m & (RS_NS - 1)) * RS_STAGE + RS_SIDE;
 #pragma unroll
@@ -1271,7 +1276,7 @@ __global__ void __launch_bounds__(FUSED_THREADS) corr_fused_kernel(const FusedPa
                 ssc[j] += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
                 float sc = 1.f;
                 if constexpr (PREC == PREC_F16X3) {
-                    if (m < 2 && bscc[j] == 0.f) {
+                    if (bscc[j] == 0.f) {
                         float mx = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
 #pragma unroll
                         for (int mm = 4; mm >= 1; mm >>= 1) mx = fmaxf(mx, __shfl_xor(mx, mm, 64));
@@ -1314,7 +1319,7 @@ __global__ void __launch_bounds__(FUSED_THREADS) corr_fused_kernel(const FusedPa
         };
         auto commit = [&](GSet& g, int m) {
             if (m < NKC) { commit_code(g, m); if (m == NKC - 1) finish_codes(); }
-            else commit_feat(g, m, m - NKC < 2);
+            else commit_feat(g, m);
         };
         // Head (static): the B sides of stages 0..3 fill the four (still free) ring slots before the first barrier, out
         // of ONE round trip: three stages in flight at once (a third register set that only lives here), the fourth
@@ -1352,7 +1357,7 @@ __global__ void __launch_bounds__(FUSED_THREADS) corr_fused_kernel(const FusedPa
             TL(n, 0);
             ring_barrier();                          // B(n)
             TL(n, 1);
-            commit_feat(ga, n + 2, false);
+            commit_feat(ga, n + 2);
             TL(n, 2);
             __builtin_amdgcn_sched_barrier(0);
             issue_feat(ga, n + 4 - NKC);
@@ -1360,7 +1365,7 @@ __global__ void __launch_bounds__(FUSED_THREADS) corr_fused_kernel(const FusedPa
             TL(n + 1, 0);
             ring_barrier();                          // B(n + 1)
             TL(n + 1, 1);
-            commit_feat(gb, n + 3, false);
+            commit_feat(gb, n + 3);
             TL(n + 1, 2);
             __builtin_amdgcn_sched_barrier(0);
             issue_feat(gb, n + 5 - NKC);
@@ -1369,7 +1374,7 @@ __global__ void __launch_bounds__(FUSED_THREADS) corr_fused_kernel(const FusedPa
 #pragma unroll
         for (int n = TAIL0; n < NT; ++n) {          // the last stages: nothing left to issue, then nothing left to commit
             ring_barrier();                          // B(n)
-            if (n + 2 < NT) { if (n & 1) commit_feat(gb, n + 2, false); else commit_feat(ga, n + 2, false); }
+            if (n + 2 < NT) { if (n & 1) commit_feat(gb, n + 2); else commit_feat(ga, n + 2); }
             if (n + 4 < NT) { if (n & 1) issue_feat(gb, n + 4 - NKC); else issue_feat(ga, n + 4 - NKC); }
         }
         // ---- 1 / ||b_j|| of the gathered feature side (F.normalize eps, modules.py:276); the anchor side is pre-normalised

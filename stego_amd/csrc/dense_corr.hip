@@ -679,9 +679,47 @@ size_t dense_workspace_bytes(int B, int C, int M, int N)
     return (size_t)B * (nbA + nbB) * NCH * DC_SIDE + (size_t)B * (nbA + nbB) * TP * sizeof(float) + 512;
 }
 
+// a channels-last map whose pixels the kernels read in 16-byte pieces (dense_prep_kernel's vec form, the row-block and the stream kernel)
+static bool dense_cl(const MapV& m, int C)
+{
+    return m.sc == 1 && C % 4 == 0 && C <= 1024 && (m.sn % 4) == 0 && (m.sh % 4) == 0 && (m.sw % 4) == 0 &&
+           (reinterpret_cast<uintptr_t>(m.p) % 16) == 0;
+}
+
+// The kernel launch_dense_corr takes (and stego_dense_corr_kernel reports), from the maps' strides and the dimensions alone.
+//   stream    (dense_stream.hip): channels-last maps, 64 < C <= 384, C % 8 == 0, B's pixels at a dense stride (pixel p at p * sw), and the two
+//             limits of its 32-bit lane offsets: an image's output is at most 2^32 bytes (store_rows: ordo + k * rowp + 4 njp TP, in unsigned),
+//             and the B stream's last byte lies within 2^32 of the image's first (load_rows: min(p, N - 1) * 4 sw + 4 (channel), in unsigned;
+//             the clamp is applied in front of the product, so the pixels the stream runs past the map's end add nothing).  Its A side and
+//             dense_stats_kernel form 64-bit addresses.
+//   row block (dense_rowblock_kernel<false> behind dense_prep_kernel for B): channels-last maps, C <= 384, C % 8 == 0.  Every address is
+//             a 64-bit pointer plus (size_t) row * N + col or long long stride products: no limit beyond MapV's.
+//   tile      (dense_tile_kernel behind dense_prep_kernel for both maps): any strides.  64-bit addresses as well, but the row blocks of A are
+//             the grid's y dimension, at most 65535 of them.
+// Every kernel's x grid (images x blocks) is formed in int and must fit one.  -1: no kernel is correct for this call.
+int dense_corr_kernel(const MapV& a, const MapV& b, int B, int C, int H1, int W1, int H2, int W2, int debug)
+{
+    const long long M = (long long)H1 * W1, N = (long long)H2 * W2;
+    const long long nbA = (M + TP - 1) / TP, nbB = (N + TP - 1) / TP, B8 = (B + 7) / 8 * 8;
+    const int NCH = (C + KC - 1) / KC;
+    constexpr long long GRID = 0x7fffffffLL, OFFS = 1LL << 32;
+    const bool rows = dense_cl(a, C) && dense_cl(b, C) && C % 8 == 0 && NCH <= DR_MAXCH && !(debug & 8192) && B8 * nbA <= GRID;      // (debug 8192: the tile kernel)
+    // round 6: the streaming kernel (dense_stream.hip) - B read as it lies and converted by the multiplying workgroups themselves, one small
+    // statistics launch in front instead of the operand prep (debug bit 21: the row-block kernel)
+    if (rows && C > KC && b.sh == (long long)W2 * b.sw && !(debug & (1 << 21)) &&
+        4 * M * N <= OFFS && (N - 1) * 4 * b.sw + 4LL * C <= OFFS && (long long)B * nbB * (TP / 32) <= GRID)
+        return STEGO_DENSE_STREAM;
+    if (rows && (long long)B * nbB <= GRID) return STEGO_DENSE_ROWBLOCK;
+    if ((long long)B * (nbA + nbB) <= GRID && nbA <= 65535) return STEGO_DENSE_TILE;
+    return -1;
+}
+
 hipError_t launch_dense_corr(const MapV& a, const MapV& b, int B, int C, int H1, int W1, int H2, int W2, int normalize,
                              float* out, void* ws, hipStream_t stream)
 {
+    const int kernel = dense_corr_kernel(a, b, B, C, H1, W1, H2, W2, knob(KNOB_DEBUG));
+    if (kernel < 0) return hipErrorInvalidValue;          // (stego_dense_corr asks first and answers STEGO_ERR_UNSUPPORTED)
+    if (kernel == STEGO_DENSE_STREAM) return launch_dense_stream(a, b, B, C, H1, W1, H2, W2, normalize, out, ws, stream);
     DenseParams prm{};
     prm.a = a; prm.b = b; prm.out = out;
     prm.B = B; prm.C = C; prm.M = H1 * W1; prm.N = H2 * W2; prm.W1 = W1; prm.W2 = W2;
@@ -693,23 +731,15 @@ hipError_t launch_dense_corr(const MapV& a, const MapV& b, int B, int C, int H1,
     prm.imgB = w + (size_t)B * prm.nbA * prm.NCH * DC_SIDE;
     prm.rsA = reinterpret_cast<float*>(w + (size_t)B * (prm.nbA + prm.nbB) * prm.NCH * DC_SIDE);
     prm.rsB = prm.rsA + (size_t)B * prm.nbA * TP;
-    auto cl = [&](const MapV& m) {
-        return m.sc == 1 && C % 4 == 0 && C <= 1024 && (m.sn % 4) == 0 && (m.sh % 4) == 0 && (m.sw % 4) == 0 &&
-               (reinterpret_cast<uintptr_t>(m.p) % 16) == 0;
-    };
-    const int vec = cl(a) && cl(b) ? 1 : 0;
-    // round 6: the streaming kernel (dense_stream.hip) - B read as it lies and converted by the multiplying workgroups themselves, one small
-    // statistics launch in front instead of the operand prep (debug bit 21: the row-block kernel below)
-    if (vec && C % 8 == 0 && C > KC && prm.NCH <= DR_MAXCH && b.sh == W2 * b.sw && !(knob(KNOB_DEBUG) & (8192 | (1 << 21))))
-        return launch_dense_stream(a, b, B, C, H1, W1, H2, W2, normalize, out, ws, stream);
-    if (vec && C % 8 == 0 && prm.NCH <= DR_MAXCH && !(knob(KNOB_DEBUG) & 8192)) {          // (debug 8192: the tile kernel)
+    if (kernel == STEGO_DENSE_ROWBLOCK) {
         // row-block kernel: the A map is consumed as it lies, only B is prepared (blocks [nbA, nbA + nbB) of every image)
         DenseParams pb = prm;
         pb.nbA = 0;                                    // the prep kernel's block index then runs over the B blocks only
-        hipLaunchKernelGGL(dense_prep_kernel, dim3((unsigned)(B * prm.nbB)), dim3(NTHREADS), 0, stream, pb, vec);
+        hipLaunchKernelGGL(dense_prep_kernel, dim3((unsigned)(B * prm.nbB)), dim3(NTHREADS), 0, stream, pb, 1);
         const int lds2 = DR_NST * DC_SIDE + 512;
         return launch<dense_rowblock_kernel<false>>(dim3((unsigned)(((B + 7) / 8) * 8 * prm.nbA)), dim3(NTHREADS), lds2, stream, prm);
     }
+    const int vec = dense_cl(a, C) && dense_cl(b, C) ? 1 : 0;
     hipLaunchKernelGGL(dense_prep_kernel, dim3((unsigned)(B * (prm.nbA + prm.nbB))), dim3(NTHREADS), 0, stream, prm, vec);
     const int lds = 2 * DC_SIDE;
     return launch<dense_tile_kernel>(dim3(prm.nbB, prm.nbA, B), dim3(NTHREADS), lds, stream, prm);

@@ -112,7 +112,7 @@ __global__ void __launch_bounds__(NTHREADS) dense_stream_kernel(const DenseStrea
     // pixels beyond N and channels beyond C are read from a clamped address and multiplied by zero (invB is 0 behind the map's last pixel).
     const int q4 = lane >> 4, s16 = lane & 15;
     const int G = prm.nbB * NCH;
-    const float* bimg = prm.b.p + (long long)n * prm.b.sn;                 // (dense pixel stride: pixel p lies at p * sw - host-checked)
+    const float* bimg = prm.b.p + (long long)n * prm.b.sn;                 // (dense pixel stride: pixel p lies at p * sw - dense_corr_kernel: b.sh == W2 * b.sw)
     const unsigned bsw4 = 4u * (unsigned)prm.b.sw;
     const float* invn = prm.invB + (size_t)n * prm.nbB * TP + 32 * wave + q4;
     float binv[8];                                   // multipliers of my eight pixels, for the block being CONVERTED (dense_stats_kernel; 0 behind the map)
@@ -123,7 +123,8 @@ __global__ void __launch_bounds__(NTHREADS) dense_stream_kernel(const DenseStrea
     f32x4 raw[8];                                    // my eight 16-byte pieces of the chunk on its way: a row pair is reloaded (chunk g + 2) right
                                                      // after it was converted (chunk g + 1) - one register set, a whole chunk of latency
     auto load_rows = [&](int nj, int c, int i0, int i1) __attribute__((always_inline)) {
-        // (uniform base + 32-bit lane offset: an image's bytes are < 2^31, host-checked - no 64-bit lane pointers to keep alive)
+        // (uniform base + 32-bit UNSIGNED lane offset - no 64-bit lane pointers to keep alive.  dense_corr_kernel sends a map here only if
+        // (N - 1) * 4 sw + 4 C <= 2^32: the clamp comes before the product, so no offset is beyond the last pixel's last channel)
         const unsigned cho = 4u * (unsigned)min(64 * c + 4 * s16, C - 4);
         const int p0 = nj * TP + 32 * wave + q4;
 #pragma unroll
@@ -157,7 +158,7 @@ __global__ void __launch_bounds__(NTHREADS) dense_stream_kernel(const DenseStrea
     const bool v4 = (prm.N & 3) == 0;
     constexpr int LO = TP * LDH;
     const float* prd = park + half * DS_PKS + 4 * r;              // my 16 bytes of row pair k: prd + 2 k DS_PKS
-    const unsigned ordo = 4u * ((unsigned)(mi * TP + 32 * wave + half) * (unsigned)prm.N + 4u * r);      // byte offset of my piece of row pair 0 (an image's output is < 2^32 bytes, host-checked)
+    const unsigned ordo = 4u * ((unsigned)(mi * TP + 32 * wave + half) * (unsigned)prm.N + 4u * r);      // byte offset of my piece of row pair 0 (dense_corr_kernel: an image's output is <= 2^32 bytes; rows beyond M may wrap, they are never stored)
     const unsigned rowp = 8u * (unsigned)prm.N;                  // bytes between row pairs
 
     // row pairs [k0, k1) of the sixteen of the parked slab of block njp: row 2 k + half, columns 4 r .. 4 r + 3 (one 512-byte run per half-wave)
@@ -446,7 +447,8 @@ size_t dense_stream_workspace_bytes(int B, int N)
     return (size_t)2 * B * ((N + TP - 1) / TP) * TP * sizeof(float) + 512;
 }
 
-// the caller (launch_dense_corr) has checked: channels-last maps, 16-byte aligned pixels, C % 8 == 0, 64 < C <= 384
+// the caller (launch_dense_corr) has asked dense_corr_kernel: channels-last maps, 16-byte aligned pixels, C % 8 == 0, 64 < C <= 384, B's pixels
+// at a dense stride, and the two 32-bit offset limits of dense_stream_kernel (output bytes per image, B's largest byte offset)
 hipError_t launch_dense_stream(const MapV& a, const MapV& b, int B, int C, int H1, int W1, int H2, int W2, int normalize, float* out, void* ws,
                                hipStream_t stream)
 {

@@ -42,6 +42,9 @@ hipError_t launch_ref_masks(unsigned long long seed, unsigned long long offset, 
 // dense_corr.hip, dense_stream.hip
 size_t dense_workspace_bytes(int B, int C, int M, int N);
 size_t dense_panel_image_bytes(int C, int P);
+// which kernel launch_dense_corr takes for these maps (STEGO_DENSE_*), or -1: none of them is correct there.  debug: knob(KNOB_DEBUG).
+// Host arithmetic on strides and dimensions only: no map data is read, nothing is launched.
+int dense_corr_kernel(const MapV& a, const MapV& b, int B, int C, int H1, int W1, int H2, int W2, int debug);
 hipError_t launch_dense_corr(const MapV& a, const MapV& b, int B, int C, int H1, int W1, int H2, int W2, int normalize,
                              float* out, void* ws, hipStream_t stream);
 hipError_t launch_dense_corr_panels(const void* imgA, const float* rsA, int imagesA, const void* imgB, const float* rsB, int B, int C, int M, int N,

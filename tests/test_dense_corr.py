@@ -201,3 +201,82 @@ def test_dense_corr_every_kernel_on_one_input(C, normalize):
     for name, out in outs.items():
         np.testing.assert_allclose(out, ref, rtol=1e-3, atol=2e-5 * max(np.abs(ref).mean(), 1e-3) + 1e-6, err_msg=name)
         assert _fp32_class_err(out, ref) < 2e-6, (name, _fp32_class_err(out, ref))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# The stream kernel's 32-bit byte offsets (csrc/dense_stream.hip: load_rows, store_rows).  dense_corr_kernel (csrc/dense_corr.hip) sends a
+# call there only while an image's output is at most 2^32 bytes and (N - 1) * 4 * b.stride_w + 4 * C <= 2^32; beyond either the maps go to
+# the row-block kernel, whose addresses are 64-bit.  Each case asks stego_dense_corr_kernel FIRST and launches only if the answer is the
+# expected one: a shape beyond a limit is never run through the stream kernel (no debug bit selects it either - bits 8192 and 1 << 21 only
+# lead away from it).  B = 1, C = 72: the narrowest width the stream kernel takes.
+_LIMIT_C = 72
+
+
+def _stream_b_stride_limit(N, C):
+    """Largest b.stride_w (a multiple of 4: 16-byte aligned pixels) with (N - 1) * 4 * stride_w + 4 * C <= 2^32."""
+    return ((2 ** 32 - 4 * C) // (4 * (N - 1))) // 4 * 4
+
+
+def _block_close(out, a_rows, b_rows, normalize, what):
+    """out [R, Q] (fp32, device) against the fp64 product of a_rows [R, C] and b_rows [Q, C], computed on the device; the two bars of
+    test_dense_stream_kernel_shapes."""
+    a64, b64 = a_rows.double(), b_rows.double()
+    if normalize:                                     # norm(): F.normalize(dim=1, eps=1e-10), modules.py:275-276
+        a64 = a64 / a64.norm(dim=1, keepdim=True).clamp_min(1e-10)
+        b64 = b64 / b64.norm(dim=1, keepdim=True).clamp_min(1e-10)
+    ref = a64 @ b64.T
+    diff = (out.double() - ref).abs()
+    assert bool(torch.isfinite(out).all()), what
+    scale = float(ref.abs().mean())
+    tol = 1e-3 * ref.abs() + (2e-5 * max(scale, 1e-3) + 1e-6)                      # assert_allclose(rtol=1e-3, atol=2e-5 * max(scale, 1e-3) + 1e-6)
+    worst = float((diff - tol).max())
+    err = float(diff.max()) / max(float(ref.abs().max()), 1e-30)                  # _fp32_class_err
+    print("%s: max |out - ref| / max |ref| = %.3g, worst margin to the allclose bar = %.3g" % (what, err, worst))
+    assert worst <= 0.0, (what, worst)
+    assert err < 2e-6, (what, err)
+
+
+@pytest.mark.parametrize("H1,W1,normalize,expect", [
+    (217, 151, True, "stream"),        # M = 32767: 2^32 - 131072 bytes of output per image, the last row pair ends 131072 bytes under the limit
+    (257, 128, False, "rowblock"),     # M = 32896: 4.3 GB; rows 32768 .. 32895 begin at byte offsets >= 2^32
+])
+def test_dense_corr_output_at_the_stream_kernels_offset_limit(H1, W1, normalize, expect):
+    from stego_amd import capi
+    C, H2, W2 = _LIMIT_C, 128, 256
+    M, N = H1 * W1, H2 * W2
+    rng = np.random.default_rng(M)
+    ta, tb = _cl_map(_varied(rng, 1, C, H1, W1)), _cl_map(_varied(rng, 1, C, H2, W2))
+    assert capi.dense_corr_kernel(ta, tb) == expect                  # the guard: nothing is launched on a surprise
+    assert (4 * M * N <= 2 ** 32) == (expect == "stream")
+    out = capi.dense_corr(ta, tb, normalize=normalize).view(M, N)
+    a_rows, b_rows = ta[0].permute(1, 2, 0).reshape(M, C), tb[0].permute(1, 2, 0).reshape(N, C)
+    cross = 2 ** 32 // (4 * N)                                       # the first row whose byte offset row * N * 4 does not fit 32 bits
+    mid = max(0, min(cross - 128, M - 256))
+    for name, r0, r1 in (("first rows", 0, 256), ("rows around 2^32 bytes", mid, mid + 256), ("last rows", M - 128, M)):
+        _block_close(out[r0:r1], a_rows[r0:r1], b_rows, normalize, "%d x %d, %s [%d, %d)" % (M, N, name, r0, r1))
+
+
+@pytest.mark.parametrize("over,normalize,expect", [
+    (True, True, "rowblock"),          # stride_w = 262400: pixel 4095 lies 4095 * 4 * 262400 = 4.298e9 > 2^32 bytes behind pixel 0
+    (False, False, "stream"),          # the largest 16-byte aligned pixel stride under the limit: the last pixel's last byte ends < 2^32
+])
+def test_dense_corr_b_pixel_stride_at_the_stream_kernels_offset_limit(over, normalize, expect):
+    """B is a 64 x 64 map of 72 channels whose pixels lie `stride_w` floats apart: channels [:72] of a [1, 4096, stride_w] buffer (1.07e9
+    elements: under the 2^31 of a map view).  Only the view is filled."""
+    from stego_amd import capi
+    C, H1, W1, H2, W2 = _LIMIT_C, 16, 16, 64, 64
+    M, N = H1 * W1, H2 * W2
+    sw = 262400 if over else _stream_b_stride_limit(N, C)
+    assert sw % 4 == 0 and ((N - 1) * 4 * sw + 4 * C > 2 ** 32) == over
+    assert over or (N - 1) * 4 * (sw + 4) + 4 * C > 2 ** 32            # ... and the next aligned stride is over it
+    rng = np.random.default_rng(sw)
+    ta = _cl_map(_varied(rng, 1, C, H1, W1))
+    buf = torch.empty(1, H2, W2, sw, dtype=torch.float32, device=DEV)
+    tb = buf[..., :C].permute(0, 3, 1, 2)
+    tb.copy_(torch.from_numpy(_varied(rng, 1, C, H2, W2)).to(DEV))
+    assert tb.stride() == (N * sw, 1, W2 * sw, sw)
+    assert capi.dense_corr_kernel(ta, tb) == expect                  # the guard: nothing is launched on a surprise
+    out = capi.dense_corr(ta, tb, normalize=normalize).view(M, N)
+    a_rows, b_rows = ta[0].permute(1, 2, 0).reshape(M, C), tb[0].permute(1, 2, 0).reshape(N, C)
+    for name, q0 in (("first", 0), ("middle", N // 2 - 64), ("last", N - 128)):
+        _block_close(out[:, q0:q0 + 128], a_rows, b_rows[q0:q0 + 128], normalize, "stride_w %d, %s B pixels [%d, %d)" % (sw, name, q0, q0 + 128))
