@@ -13,7 +13,8 @@
  * (x = hi + lo to 2^-22: the fp32 class the reference's fp32 torch model computes in, and what the loss kernels and the
  * segmentation head of this library use), in STEGO_VIT_F16 as plain fp16 operands (2 - 3 x faster, error at the level of
  * torch's fp16 autocast).  Measured deviations from the fp32 / fp64 torch model: DESIGN.md 4.9 / tests/test_vit_native.py.
- * The attention maps and the qkv tensor the reference materialises at every block (:232-236) are never built.
+ * The attention maps and the qkv tensor the reference materialises at every block (:232-236) are never built; the keys of the last
+ * block, the reference's feature type "KK", come from stego_vit_forward_keys.
  *
  * Conventions as in stego_corr.h: device pointers, nothing allocated / freed / synchronised, work enqueued on
  * `stream`, return STEGO_OK or an error code.
@@ -64,6 +65,21 @@ int stego_vit_pack_weights(const StegoVitDesc* d, const float* const* params, in
 size_t stego_vit_workspace_bytes(const StegoVitDesc* d);
 int stego_vit_forward(const StegoVitDesc* d, const void* packed, const float* img, float* tokens_out, void* workspace,
                       size_t workspace_bytes, stego_stream_t stream);
+
+/* The attention keys of the LAST block instead of the normalised tokens: the reference's other feature type,
+ *   src/modules.py:98-101                    DinoFeaturizer.forward, feat_type == "KK": qkv[1, :, :, 1:, :] -> [B, heads * 64, h, w]
+ *   src/dino/vision_transformer.py:78-81     Attention.forward: qkv = self.qkv(x).reshape(B, N, 3, heads, C // heads).permute(2, 0, 3, 1, 4)
+ *   src/dino/vision_transformer.py:232-236   get_intermediate_feat: the qkv tensor of the block (only its K third is computed here)
+ * keys_out: OUT fp32 [B, 1 + hw, D], row t of image b = LN1(x) . W_qkv[D:2D]^T + b_qkv[D:2D] of token t in block depth-1, channel
+ * head * 64 + d = qkv[1][b, head, t, d].  Row 0 is the class token's key; keys_out[:, 1:, :] viewed as [B, h, w, D] is the channels-last
+ * key map - same shape and row order as tokens_out, so everything downstream of the tokens takes it unchanged.  (The reference
+ * hard-codes 6 heads at modules.py:99; the channel order here is that of the model's own head count, the same thing for ViT-S.)
+ * Same descriptor, same packed weights, same stego_vit_workspace_bytes, same argument checks in the same order as stego_vit_forward.
+ * Runs prepare_tokens and blocks 0 .. depth-2 as stego_vit_forward does, then LN1 and the K columns of the QKV GEMM of block depth-1
+ * and nothing else (no Q / V columns, attention, proj, MLP or final norm; depth == 1 is legal).  The keys leave the GEMM's fp32
+ * accumulators directly: F16X3 keys are fp32 class, F16 keys carry the operand rounding only. */
+int stego_vit_forward_keys(const StegoVitDesc* d, const void* packed, const float* img, float* keys_out, void* workspace,
+                           size_t workspace_bytes, stego_stream_t stream);
 
 #ifdef __cplusplus
 }

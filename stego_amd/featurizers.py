@@ -226,6 +226,18 @@ class DinoFeaturizer(nn.Module):
         return nn.Sequential(nn.Conv2d(in_channels, in_channels, (1, 1)), nn.ReLU(),
                              nn.Conv2d(in_channels, self.dim, (1, 1)))
 
+    def _native_backbone(self, img, n):
+        """The NativeViT of this backbone if the hand-written kernels of include/stego_vit.h take this batch (a HIP device, fp32, n == 1,
+        cfg.native_backbone - True unless set False -, a geometry and a shape the library builds), else None."""
+        if not (img.is_cuda and n == 1 and img.dtype == torch.float32 and getattr(self.cfg, "native_backbone", True)
+                and vit_native.supported(self.model)):
+            return None
+        if self._native is None:
+            self._native = vit_native.NativeViT(self.model, precision=getattr(self.cfg, "backbone_precision", "f16x3"))
+        if not self._native.shape_supported(*[int(img.shape[i]) for i in (0, 2, 3)]):
+            return None
+        return self._native
+
     def _tokens(self, img, n):
         """feat[0] (and qkv[0]) of get_intermediate_feat (modules.py:88-89).  On a HIP device the frozen backbone runs on the
         hand-written kernels of include/stego_vit.h - DEFAULT (cfg.native_backbone, True unless set False) in precision
@@ -233,20 +245,21 @@ class DinoFeaturizer(nn.Module):
         residual stream; its error against the fp64 model is at or below the fp32 torch model's own (tests/test_vit_native.py:
         4e-7 .. 4e-5 depending on the network), at half the fp32 torch module's time.  "f16" (opt-in) is the plain fp16-operand
         path: another 2x faster, 5e-4 .. 1e-3 relative L2 with single elements up to 4e-2 off - outside the fp32 class.  The torch
-        module is kept for the variants the kernels do not build: n > 1, feat_type 'KK' (needs the block's qkv), CPU tensors,
-        geometries outside include/stego_vit.h."""
-        native_ok = (img.is_cuda and n == 1 and self.feat_type == "feat" and img.dtype == torch.float32
-                     and getattr(self.cfg, "native_backbone", True) and vit_native.supported(self.model))
-        if native_ok:
-            if self._native is None:
-                self._native = vit_native.NativeViT(self.model, precision=getattr(self.cfg, "backbone_precision", "f16x3"))
-            if self._native.shape_supported(*[int(img.shape[i]) for i in (0, 2, 3)]):      # (else: the torch module below)
-                self.backbone_path = "native"
-                return self._native.forward_tokens(img), None
+        module is kept for what the kernels do not build: n > 1, the whole qkv tensor (feat_type 'KK' where forward() cannot have the
+        native keys of _keys: cfg.native_backbone not set), CPU tensors, geometries outside include/stego_vit.h."""
+        native = self._native_backbone(img, n) if self.feat_type == "feat" else None
+        if native is not None:
+            self.backbone_path = "native"
+            return native.forward_tokens(img), None
         self.backbone_path = "torch"
         feat, _, qkv = self.model.get_intermediate_feat(img, n=n)
         return feat[0], qkv[0]
 
+    def _keys(self, img):
+        """feat_type 'KK' (modules.py:98-101) on the native backbone: the last block's attention keys [B, 1 + hw, D], channel
+        head * 64 + d, rows as in the tokens (NativeViT.forward_keys: the last block stops after the K third of its QKV GEMM)."""
+        self.backbone_path = "native"
+        return self._native.forward_keys(img)
 
     def enable_token_cache(self, n_items, img_hw, device, dtype=torch.float16):
         """Keep the backbone tokens of dataset items 0..n_items-1 in device memory (see TokenCache)."""
@@ -259,14 +272,27 @@ class DinoFeaturizer(nn.Module):
             self.model.eval()
         with torch.no_grad():
             assert img.shape[2] % self.patch_size == 0 and img.shape[3] % self.patch_size == 0
-            if cache_index is not None and self.token_cache is not None and n == 1 and self.feat_type == "feat":
+            cached = cache_index is not None and self.token_cache is not None and n == 1
+            # 'KK' on the native backbone: `feat` holds the keys, in the tokens' layout (and so does the TokenCache then: one feature type
+            # per featurizer).  The class feature is the class row of the TOKENS whatever the feature type (modules.py:105-106): under 'KK'
+            # it takes the token forward and never the cache.  'KK' was computed by the fp32 torch module before the kernels had keys:
+            # a cfg that does not carry the key `native_backbone` at all keeps that (for 'feat' a missing key means True, as it always
+            # did); configs/train_config.yml sets it, so every cfg made by load_config has the native keys
+            native_kk = self._native_backbone(img, n) if self.feat_type == "KK" and getattr(self.cfg, "native_backbone", None) else None
+            native_keys = native_kk is not None and not return_class_feat
+            if native_keys:
+                feat, qkv = (self.token_cache.fetch(cache_index, img, self._keys) if cached else self._keys(img)), None
+            elif native_kk is not None:
+                self.backbone_path = "native"
+                feat, qkv = native_kk.forward_tokens(img), None
+            elif cached and self.feat_type == "feat":
                 feat, qkv = self.token_cache.fetch(cache_index, img, lambda sub: self._tokens(sub, 1)[0]), None
             else:
                 feat, qkv = self._tokens(img, n)
             fh, fw = img.shape[2] // self.patch_size, img.shape[3] // self.patch_size
             if return_class_feat:
                 return feat[:, :1, :].reshape(feat.shape[0], 1, 1, -1).permute(0, 3, 1, 2)
-            if self.feat_type == "feat":
+            if self.feat_type == "feat" or native_keys:
                 image_feat = feat[:, 1:, :].reshape(feat.shape[0], fh, fw, -1).permute(0, 3, 1, 2)
             elif self.feat_type == "KK":
                 k = qkv[1, :, :, 1:, :]

@@ -2,9 +2,10 @@
 
 Host-side mirror of what ``DinoFeaturizer.forward`` needs from the reference's
 ``VisionTransformer.get_intermediate_feat(img, n=1)`` (src/dino/vision_transformer.py:225-237, called at
-src/modules.py:88): the normalised tokens of the last block.  The reference also returns the attention maps and the
-qkv tensor of that block; ``feat_type == "feat"`` (the default, train_config.yml) never looks at them, so this path
-does not build them - callers that want ``feat_type == "KK"`` or ``n > 1`` keep using the torch module.
+src/modules.py:88): the normalised tokens of the last block (``forward_tokens``, ``feat_type == "feat"``, the default of
+train_config.yml) or that block's attention keys (``forward_keys``, ``feat_type == "KK"``, src/modules.py:98-101).  The
+reference also returns the attention maps and the whole qkv tensor of the block; neither feature type looks at more than the
+K third, so this path does not build them - callers that want ``n > 1`` keep using the torch module.
 
 Weights are packed once per (H, W) from a ``dino_vit.VisionTransformer`` (same parameter names as the DINO
 checkpoints); torch is used for device memory and for the bicubic ``interpolate_pos_encoding`` only.
@@ -43,7 +44,7 @@ PRECISIONS = {"f16x3": capi.VIT_F16X3, "f16": capi.VIT_F16}
 
 
 class NativeViT:
-    """Packed weights + workspace cache around stego_vit_forward for one frozen ``dino_vit.VisionTransformer``.
+    """Packed weights + workspace cache around stego_vit_forward / stego_vit_forward_keys for one frozen ``dino_vit.VisionTransformer``.
 
     precision "f16x3" (default): split-fp16 operands, three MFMAs per product - the fp32 class of the reference's torch model;
     "f16": plain fp16 operands, 2 - 3 x faster, error at the level of torch's fp16 autocast (include/stego_vit.h)."""
@@ -93,6 +94,15 @@ class NativeViT:
 
     def forward_tokens(self, img):
         """img fp32 [B,3,H,W] on a HIP device -> tokens fp32 [B, 1 + hw, D] (= feat[0] of get_intermediate_feat(n=1))."""
+        return self._forward(img, "stego_vit_forward")
+
+    def forward_keys(self, img):
+        """img fp32 [B,3,H,W] on a HIP device -> the last block's attention keys fp32 [B, 1 + hw, D], channel head * 64 + d
+        (= qkv[0][1] of get_intermediate_feat(n=1) as [B, token, head, d]): row 0 the class token's key, rows 1.. the channels-last
+        key map.  The last block stops after the K third of its QKV GEMM; same packed weights and workspace as forward_tokens."""
+        return self._forward(img, "stego_vit_forward_keys")
+
+    def _forward(self, img, entry):
         capi._require_dev(img)
         if img.dtype != torch.float32 or img.dim() != 4 or img.shape[1] != 3:
             raise RuntimeError("stego_vit: expected a float32 [B,3,H,W] image batch, got %s %s" % (img.dtype, tuple(img.shape)))
@@ -114,6 +124,6 @@ class NativeViT:
         ps = self.model.patch_embed.patch_size
         out = torch.empty(B, 1 + (H // ps) * (W // ps), self.model.embed_dim, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            capi._check(lib.stego_vit_forward(ctypes.byref(desc), blob.data_ptr(), img.data_ptr(), out.data_ptr(), ws.data_ptr(),
-                                              ws.numel(), capi._stream()))
+            capi._check(getattr(lib, entry)(ctypes.byref(desc), blob.data_ptr(), img.data_ptr(), out.data_ptr(), ws.data_ptr(),
+                                            ws.numel(), capi._stream()))
         return out

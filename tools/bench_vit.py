@@ -1,6 +1,8 @@
 #!/usr/bin/env python
 """Frozen DINO backbone forward: native kernels vs torch on the same GPU and vs the CPU.
-One JSON line.  FLOPs counted: patch GEMM + per block (qkv, proj, fc1, fc2 GEMMs + QK^T + PV)."""
+One JSON line.  FLOPs counted: patch GEMM + per block (qkv, proj, fc1, fc2 GEMMs + QK^T + PV).
+--feat-type KK times NativeViT.forward_keys (the last block's attention keys: that block stops after the K third of its QKV GEMM), with
+forward_tokens in the same process and the torch module's get_intermediate_feat - what a 'KK' featurizer ran before - beside it."""
 import argparse, json, os, sys, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,6 +15,7 @@ ap.add_argument("--size", type=int, default=224); ap.add_argument("--batch", typ
 ap.add_argument("--iters", type=int, default=10); ap.add_argument("--no-cpu", action="store_true")
 ap.add_argument("--no-torch", action="store_true")
 ap.add_argument("--precision", default="f16x3", choices=["f16x3", "f16"])
+ap.add_argument("--feat-type", default="feat", choices=["feat", "KK"])
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 torch.manual_seed(0)
@@ -33,6 +36,23 @@ def timed(fn, iters):
 nat = vit_native.NativeViT(model, precision=a.precision)
 x3 = a.precision == "f16x3"
 peak = 2500.0 / 3 if x3 else 2500.0      # f16x3: three MFMAs per product
+if a.feat_type == "KK":
+    ms_tokens = timed(lambda: nat.forward_tokens(img), a.iters)
+    ms_keys = timed(lambda: nat.forward_keys(img), a.iters)
+    ms_tokens2 = timed(lambda: nat.forward_tokens(img), a.iters)          # once more after the keys: drift of the visit
+    out = {"metric": "frozen DINO %s/%d last-block keys, %dx%d" % (a.arch, a.patch, a.size, a.size), "batch": a.batch, "unit": "images/s",
+           "value": a.batch / ms_keys * 1e3, "forward_keys_ms": ms_keys, "forward_tokens_ms": ms_tokens, "forward_tokens_again_ms": ms_tokens2,
+           "keys_over_tokens": ms_keys / min(ms_tokens, ms_tokens2), "precision": a.precision, "iters": a.iters}
+    if not a.no_torch:
+        with torch.no_grad():
+            ms32 = timed(lambda: model.get_intermediate_feat(img, n=1), max(2, a.iters // 3))
+            ref = model.get_intermediate_feat(img, n=1)[2][0][1].permute(0, 2, 1, 3).reshape(a.batch, ntok, D)
+        got = nat.forward_keys(img)
+        out["torch_get_intermediate_feat_fp32_ms"] = ms32
+        out["speedup_vs_torch_fp32"] = ms32 / ms_keys
+        out["rel_l2_vs_torch_fp32"] = float((got - ref).norm() / ref.norm())
+    print(json.dumps(out))
+    sys.exit(0)
 ms_native = timed(lambda: nat.forward_tokens(img), a.iters)
 out = {"metric": "frozen DINO %s/%d forward, %dx%d" % (a.arch, a.patch, a.size, a.size), "batch": a.batch, "unit": "images/s",
        "value": a.batch / ms_native * 1e3, "ms": ms_native, "effective_TFLOPs": flops / ms_native / 1e9,
