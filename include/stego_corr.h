@@ -33,7 +33,7 @@ extern "C" {
                                 * 5: stego_corr_event_counters
                                 * 6: StegoVitDesc.precision (STEGO_VIT_F16X3: the backbone in the fp32 class)
                                 * 7: stego_sample, stego_sample_bwd, stego_rowsum, stego_loss_pointwise_fwd / _bwd, stego_sample_panels, stego_dense_corr_panels, stego_sample_bwd_rows; stego_corr_fwd / _bwd take S = 12 .. 16
-                                *    (entry points added since, here stego_dense_corr_kernel, and the other headers' are additions: no existing
+                                *    (entry points added since, here stego_dense_corr_kernel, and the other headers' - stego_data_prepare_dir, stego_salience_coords - are additions: no existing
                                 *    signature or struct changed, the number stays) */
 
 enum {

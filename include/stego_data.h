@@ -74,6 +74,17 @@ int stego_data_prepare(const StegoDataDesc* desc, const StegoDataItem* items, co
                        const int32_t* map_pool, const float* lut, const int64_t* index, const int32_t* origin, float* img,
                        int64_t* label, uint8_t* mask, stego_stream_t stream);
 
+/* The same batch for a directory store (the user's own image folder, data.py DirectoryDataset): descriptor, records, maps, lut, index
+ * and origin as for stego_data_prepare, with the directory dataset's label rule:
+ *     label[n, y, x]   = lab[row_map[top + y], col_map[left + x]]          (int64: the stored byte itself, no "- 1")
+ *     mask[n, 0, y, x] = label[n, y, x] > 0 ? 1.0f : 0.0f                  (float32: the salience mask of cfg.use_salience)
+ * `label_arena` may be NULL - a folder without labels: label is -1 everywhere and mask 0; the records' label_offset and
+ * desc.label_arena_bytes are then not used.  mask : float32 [N, 1, R, R].  The same host checks and error codes, with the float mask
+ * aligned like img (16 bytes when R % 4 == 0, else 4), all before anything is enqueued.  Deterministic, no atomics. */
+int stego_data_prepare_dir(const StegoDataDesc* desc, const StegoDataItem* items, const uint8_t* img_arena, const uint8_t* label_arena,
+                           const int32_t* map_pool, const float* lut, const int64_t* index, const int32_t* origin, float* img,
+                           int64_t* label, float* mask, stego_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -197,6 +197,15 @@ class StegoAdamDesc(Structure):
         [("grad_elems", c_int64), ("state_elems", c_int64), ("groups", StegoAdamGroup * ADAM_MAX_GROUPS)]
 
 
+class StegoSalienceDesc(Structure):
+    """include/stego_salience.h"""
+    _fields_ = [(n, c_int32) for n in ("B", "H", "W", "S", "mask_dtype")]
+
+
+SALIENCE_ERR_SIZE, SALIENCE_ERR_SAMPLES, SALIENCE_ERR_DTYPE = 130, 131, 132
+SALIENCE_U8, SALIENCE_F32 = 0, 1
+SALIENCE_MAX_PIXELS, SALIENCE_MAX_S, SALIENCE_MAX_B = 1 << 20, 16, 65535
+
 _H = POINTER(StegoHeadDesc)
 _D = POINTER(StegoCorrDesc)
 _M = POINTER(StegoMap)
@@ -217,6 +226,8 @@ SIGNATURES = {
     "stego_crf_lattice_info": (c_int32, [POINTER(StegoCrfDesc), _P, c_size_t, c_int32, c_int32, POINTER(c_int32), _P, c_int32, _P]),
     "stego_data_check_items": (c_int32, [POINTER(StegoDataDesc), _P, POINTER(c_int64)]),
     "stego_data_prepare": (c_int32, [POINTER(StegoDataDesc)] + [_P] * 10 + [_P]),
+    "stego_data_prepare_dir": (c_int32, [POINTER(StegoDataDesc)] + [_P] * 10 + [_P]),
+    "stego_salience_coords": (c_int32, [POINTER(StegoSalienceDesc)] + [_P] * 8 + [_P]),
     "stego_probe_head": (c_int32, [POINTER(StegoProbeDesc), _M, _M] + [_P] * 5 + [_P]),
     "stego_probe_head_plan": (c_size_t, [POINTER(StegoProbeDesc), POINTER(c_int32), POINTER(c_int32)]),
     "stego_stitch_probe": (c_int32, [POINTER(StegoStitchDesc), _M, _M] + [_P] * 5 + [_P]),
@@ -1132,6 +1143,61 @@ def data_prepare(desc_args, items, img_arena, label_arena, map_pool, lut, index,
     mask = torch.empty(N, 1, R, R, dtype=torch.bool, device=dev)
     _check(data_prepare_raw(desc, items, img_arena, label_arena, map_pool, lut, index, origin, img, label, mask))
     return img, label, mask
+
+
+def data_prepare_dir_raw(desc, items, img_arena, label_arena, map_pool, lut, index, origin, img, label, mask):
+    """stego_data_prepare_dir with every buffer given (label_arena None: a store without labels) -> the return code, unchecked."""
+    with _on_device(img.device if img is not None else index.device):
+        return int(load().stego_data_prepare_dir(byref(desc), _ptr(items), _ptr(img_arena), _ptr(label_arena), _ptr(map_pool), _ptr(lut),
+                                                 _ptr(index), _ptr(origin), _ptr(img), _ptr(label), _ptr(mask), _stream()))
+
+
+def data_prepare_dir(desc_args, items, img_arena, label_arena, map_pool, lut, index, origin=None):
+    """stego_data_prepare_dir (a directory store; label_arena None when the folder has no labels): as data_prepare, with
+    label = the stored byte (or -1) and mask float32 [N,1,R,R] = label > 0."""
+    _require_dev(items, img_arena, label_arena, map_pool, lut, index, origin)
+    R = int(desc_args[0])
+    N = int(index.numel())
+    dev = index.device
+    desc = data_desc(N, *desc_args)
+    img = torch.empty(N, 3, R, R, dtype=torch.float32, device=dev)
+    label = torch.empty(N, R, R, dtype=torch.int64, device=dev)
+    mask = torch.empty(N, 1, R, R, dtype=torch.float32, device=dev)
+    _check(data_prepare_dir_raw(desc, items, img_arena, label_arena, map_pool, lut, index, origin, img, label, mask))
+    return img, label, mask
+
+
+# ---- salience-guided coordinate draws (include/stego_salience.h; modules.ContrastiveCorrelationLoss.draw with cfg.native_salience)
+def salience_covers(B, H, W, S):
+    """The limits of stego_salience_coords (anything else keeps the torch path)."""
+    return 1 <= S <= SALIENCE_MAX_S and 1 <= B <= SALIENCE_MAX_B and H >= 1 and W >= 1 and H * W <= SALIENCE_MAX_PIXELS
+
+
+def salience_coords(mask1, mask2, u, u_mix, reg1, reg2):
+    """stego_salience_coords: mask1 / mask2 [B, H, W] (uint8, bool or float32), u float32 [2, B, S, S, 3], u_mix float32 [B, S, S],
+    reg1 / reg2 float32 [B, S, S, 2] -> (coords1, coords2) float32 [B, S, S, 2].  One launch, no host synchronisation."""
+    _require_dev(mask1, mask2, u, u_mix, reg1, reg2)
+    B, H, W = mask1.shape
+    S = int(u_mix.shape[1])
+    if mask1.dtype != mask2.dtype or mask1.shape != mask2.shape:
+        raise ValueError("the two salience masks differ in dtype or shape: %s %s, %s %s"
+                         % (mask1.dtype, tuple(mask1.shape), mask2.dtype, tuple(mask2.shape)))
+    if mask1.dtype == torch.float32:
+        kind = SALIENCE_F32
+    elif mask1.dtype in (torch.uint8, torch.bool):
+        kind = SALIENCE_U8
+    else:
+        raise ValueError("salience masks must be uint8, bool or float32, got %s" % mask1.dtype)
+    if tuple(u.shape) != (2, B, S, S, 3) or tuple(u_mix.shape) != (B, S, S) or tuple(reg1.shape) != (B, S, S, 2) or \
+            tuple(reg2.shape) != (B, S, S, 2) or any(t.dtype != torch.float32 for t in (u, u_mix, reg1, reg2)):
+        raise ValueError("salience_coords: u [2,B,S,S,3], u_mix [B,S,S], reg [B,S,S,2] float32 expected for B = %d, S = %d" % (B, S))
+    mask1, mask2, u, u_mix, reg1, reg2 = (t.contiguous() for t in (mask1, mask2, u, u_mix, reg1, reg2))
+    coords1, coords2 = torch.empty_like(reg1), torch.empty_like(reg2)
+    desc = StegoSalienceDesc(int(B), int(H), int(W), S, kind)
+    with _on_device(mask1.device):
+        _check(load().stego_salience_coords(byref(desc), _ptr(mask1), _ptr(mask2), _ptr(u), _ptr(u_mix), _ptr(reg1), _ptr(reg2),
+                                            _ptr(coords1), _ptr(coords2), _stream()))
+    return coords1, coords2
 
 
 # ---- fused probe head (include/stego_probe.h; stego_amd.segment wraps it for a model)

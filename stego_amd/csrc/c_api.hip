@@ -18,6 +18,7 @@
 #include "../../include/stego_confusion.h"
 #include "../../include/stego_optim.h"
 #include "../../include/stego_stitch.h"
+#include "../../include/stego_salience.h"
 #include "corr_wide.h"
 #include "launchers.h"
 
@@ -369,6 +370,9 @@ const char* stego_error_string(int code)
         case STEGO_ERR_STITCH_WINDOWS: return "stitch: T is not the layout's ny * nx windows";
         case STEGO_ERR_STITCH_OUTPUT: return "stitch: unknown output kind, or both probes skipped";
         case STEGO_ERR_STITCH_RANGE: return "stitch: window_gather's t0 < 0, n outside [1, 65535] or t0 + n beyond the layout's windows";
+        case STEGO_ERR_SALIENCE_SIZE: return "salience draws: B outside [1, 65535], H or W < 1, or H * W > 2^20 (include/stego_salience.h)";
+        case STEGO_ERR_SALIENCE_SAMPLES: return "salience draws: S outside [1, 16]";
+        case STEGO_ERR_SALIENCE_DTYPE: return "salience draws: mask_dtype is neither STEGO_SALIENCE_U8 nor STEGO_SALIENCE_F32";
         case STEGO_ERR_CRF_RANGE: return "dense CRF: a lattice coordinate would leave the packed key (image too large for its standard deviations)";
         default: return code >= STEGO_ERR_HIP ? "HIP runtime error (code - 1000 = hipError_t)" : "unknown error";
     }

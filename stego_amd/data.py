@@ -5,7 +5,11 @@
 
 written by `src/crop_datasets.py:76-123` (five crops per source image: image i * 5 + crop number; labels stored + 1 as uint8 PNG so
 that "unlabelled" -1 becomes 0) and read by `CroppedDataset` `src/data.py:370-400` (target - 1, mask = target == -1).
-torchvision is not part of this image: crops and tensor conversion are done with PIL / numpy / torch directly."""
+torchvision is not part of this image: crops and tensor conversion are done with PIL / numpy / torch directly.
+
+And the reader of a user's own image folder, the reference's DirectoryDataset (dataset_name "directory"):
+
+    {root}/{dir_dataset_name}/imgs/{split}/*        and, optionally,        {root}/{dir_dataset_name}/labels/{split}/*"""
 import os
 import random
 from os.path import join
@@ -195,9 +199,78 @@ class CroppedDataset(Dataset):
         return image, target.squeeze(0), target == -1
 
 
+LABEL_MODES = ("L", "P")            # 8-bit single-channel label files: the stored byte (or palette index) is the label
+
+
+def open_label(path):
+    """The label file `path` as a loaded PIL image of mode L or P; anything else (16-bit, RGB, bilevel ...) is a ValueError that
+    names the file."""
+    with Image.open(path) as lab:
+        if lab.mode not in LABEL_MODES:
+            raise ValueError("%s: label files must be 8-bit single-channel images (PIL mode L or P), got mode %r" % (path, lab.mode))
+        return lab.copy()
+
+
+class DirectoryDataset(Dataset):
+    """A folder of the user's own images, the reference's DirectoryDataset (src/data.py:75-118):
+
+        {root}/{path}/imgs/{split}/*          images, any format PIL reads
+        {root}/{path}/labels/{split}/*        optional: one label image per image
+
+    Both listings are sorted and pair up by position; their counts must agree and the split must not be empty.  Item i is (image,
+    label, mask): image and label go through `transform` / `target_transform` under one seed drawn from numpy's global generator (as
+    CroppedDataset does), the label is the stored value itself (no "- 1"), -1 everywhere when the folder has no `labels`, and
+    mask = (label > 0) as float32: the foreground / salience mask cfg.use_salience reads.
+
+    Three deviations from the reference:
+      * images are .convert("RGB") (the reference hands a grey or RGBA file to Normalize as it is);
+      * the label is always [H, W] int64 and the mask [1, H, W] float32, the ranks of CroppedDataset's items (the reference gives
+        [1, H, W] labels for labelled folders and [H, W] for unlabelled ones);
+      * a label file must decode to an 8-bit single-channel array (PIL mode L or P), else ValueError with the file's name."""
+
+    def __init__(self, root, path, image_set, transform=to_tensor, target_transform=to_target_tensor):
+        super().__init__()
+        self.split = image_set
+        self.transform, self.target_transform = transform, target_transform
+        self.dir = join(root, path)
+        self.img_dir, self.label_dir = join(self.dir, "imgs", image_set), join(self.dir, "labels", image_set)
+        self.img_files, self.label_files = directory_files(root, path, image_set)
+
+    def __len__(self):
+        return len(self.img_files)
+
+    def __getitem__(self, index):
+        seed = int(np.random.randint(2147483647))
+        with Image.open(self.img_files[index]) as im:
+            image = _seeded(self.transform, im.convert("RGB"), seed)
+        if self.label_files is not None:
+            label = _seeded(self.target_transform, open_label(self.label_files[index]), seed)
+            label = label.reshape(label.shape[-2:])
+        else:
+            label = torch.zeros(image.shape[1], image.shape[2], dtype=torch.int64) - 1
+        return image, label, (label > 0).to(torch.float32).unsqueeze(0)
+
+
+def directory_files(root, path, image_set):
+    """(image paths, label paths or None) of DirectoryDataset's split, both sorted by file name."""
+    d = join(root, path)
+    img_dir, label_dir = join(d, "imgs", image_set), join(d, "labels", image_set)
+    imgs = [join(img_dir, f) for f in sorted(os.listdir(img_dir))]
+    if not imgs:
+        raise ValueError("%s: empty split %r" % (d, image_set))
+    if not os.path.exists(join(d, "labels")):
+        return imgs, None
+    labels = [join(label_dir, f) for f in sorted(os.listdir(label_dir))]
+    if len(imgs) != len(labels):
+        raise AssertionError("%s: %d images but %d labels" % (d, len(imgs), len(labels)))
+    return imgs, labels
+
+
 class ContrastiveSegDataset(Dataset):
     """The reference's training / evaluation dataset (src/data.py:419-565) for the cropped trees (cocostuff27, cityscapes with a
-    crop_type): CroppedDataset items at `transform` / `target_transform`, and with pos_images / pos_labels a KNN positive per item,
+    crop_type) and for dataset_name "directory" with crop_type None (DirectoryDataset of cfg.dir_dataset_name, n_classes =
+    cfg.dir_dataset_n_classes; the table's name then carries cfg.dir_dataset_name and the literal "None"):
+    CroppedDataset / DirectoryDataset items at `transform` / `target_transform`, and with pos_images / pos_labels a KNN positive per item,
     nns[ind][r] with r uniform in [1, num_neighbors] from the precomputed table {pytorch_data_dir}/nns/nns_{model_type}_{dataset}_
     {image_set}_{crop_type}_{res}.npz.  The random draws come in the reference's order: the item's own CroppedDataset seed (numpy),
     torch.randint for the neighbour rank, the positive's CroppedDataset seed, then one more numpy seed that reseeds python's and
@@ -212,19 +285,26 @@ class ContrastiveSegDataset(Dataset):
                  aug_geometric_transform=None, aug_photometric_transform=None, num_neighbors=5, compute_knns=False, mask=False,
                  pos_labels=False, pos_images=False, extra_transform=None, model_type_override=None):
         super().__init__()
-        if crop_type is None or dataset_name not in ("cocostuff27", "cityscapes"):
-            raise ValueError("ContrastiveSegDataset reads the cropped trees only (cocostuff27 / cityscapes with a crop_type), "
-                             "got dataset %r, crop_type %r" % (dataset_name, crop_type))
+        directory = dataset_name == "directory" and crop_type is None
+        if not directory and (crop_type is None or dataset_name not in ("cocostuff27", "cityscapes")):
+            raise ValueError("ContrastiveSegDataset reads the cropped trees (cocostuff27 / cityscapes with a crop_type) and image "
+                             "folders (directory with crop_type None), got dataset %r, crop_type %r" % (dataset_name, crop_type))
         if aug_geometric_transform is not None or aug_photometric_transform is not None:
             raise ValueError("the img_aug / coord_aug augmentations are not supported")
         self.num_neighbors, self.image_set, self.dataset_name = num_neighbors, image_set, dataset_name
         self.mask, self.pos_labels, self.pos_images, self.extra_transform = mask, pos_labels, pos_images, extra_transform
-        self.n_classes = 27
-        self.dataset = CroppedDataset(pytorch_data_dir, dataset_name, crop_type, cfg.crop_ratio, image_set, transform=transform,
-                                      target_transform=target_transform)
+        if directory:
+            self.n_classes = cfg.dir_dataset_n_classes
+            self.dataset = DirectoryDataset(pytorch_data_dir, cfg.dir_dataset_name, image_set, transform=transform,
+                                            target_transform=target_transform)
+        else:
+            self.n_classes = 27
+            self.dataset = CroppedDataset(pytorch_data_dir, dataset_name, crop_type, cfg.crop_ratio, image_set, transform=transform,
+                                          target_transform=target_transform)
         model_type = model_type_override if model_type_override is not None else cfg.model_type
-        feature_cache_file = join(pytorch_data_dir, "nns", "nns_{}_{}_{}_{}_{}.npz".format(
-            model_type, dataset_name, image_set, crop_type, cfg.res))
+        from .precompute_knns import nns_filename
+        nice_dataset_name = cfg.dir_dataset_name if directory else dataset_name
+        feature_cache_file = join(pytorch_data_dir, "nns", nns_filename(model_type, nice_dataset_name, image_set, crop_type, cfg.res))
         self.feature_cache_file = feature_cache_file
         if pos_labels or pos_images:
             if not os.path.exists(feature_cache_file) or compute_knns:

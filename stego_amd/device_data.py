@@ -4,7 +4,9 @@ The reference feeds every training step from CPU workers (data.py ContrastiveSeg
 ToTensor, Normalize per item).  Here the split is decoded once, its RGB and label bytes are uploaded once, and every batch - anchors
 and KNN positives together - comes out of one launch of stego_data_prepare (include/stego_data.h, csrc/batch_prep.hip):
 
-  DeviceImageStore           the decoded split on the device: two byte arenas, a record per crop, PIL's NEAREST index maps per R
+  DeviceImageStore           the decoded split on the device: two byte arenas, a record per crop, PIL's NEAREST index maps per R;
+                             .from_directory: a user's image folder (data.DirectoryDataset) instead of a cropped split, with or
+                             without labels, optionally reduced to one resolution (store_res); batches from stego_data_prepare_dir
   DeviceContrastiveLoader    batches with the reference's keys (ind, img, label, mask, img_pos, ind_pos, label_pos, mask_pos) as
                              device tensors, in DistributedSampler's epoch order; or, without a neighbour table, the split in order
                              (img, label, mask, ind) for validation and the KNN precompute
@@ -23,7 +25,7 @@ import torch
 from PIL import Image
 
 from . import capi
-from .data import _MEAN, _STD, crop_dir, resized_size
+from .data import _MEAN, _STD, _resize, crop_dir, directory_files, open_label, resized_size
 
 DEFAULT_MAX_BYTES = 200 * 2 ** 30          # of the MI355X's 288 GB: what the split may take on the device (images + labels)
 
@@ -97,6 +99,26 @@ def split_bytes(root, dataset_name, crop_type, crop_ratio, split):
     return sum(w * h * 4 for w, h in sizes)
 
 
+def _reduce(im, store_res):
+    """What a directory store keeps of a decoded image or label: data._resize(im, store_res) when that makes it smaller (short side
+    above store_res), else the image itself - an image at or below store_res is upscaled by prepare's index maps, not in the store."""
+    return im if store_res is None or min(im.size) <= store_res else _resize(im, store_res)
+
+
+def _stored_sizes(files, store_res, threads):
+    """(w, h) of every image as a directory store keeps it (_reduce), from the headers alone."""
+    sizes = _sizes([(f,) for f in files], threads)
+    return [(w, h) if store_res is None or min(w, h) <= store_res else resized_size(w, h, store_res) for w, h in sizes]
+
+
+def directory_bytes(root, path, split, store_res=None):
+    """Device bytes DeviceImageStore.from_directory(root, path, split, store_res=store_res) takes (RGB bytes, and label bytes when
+    the folder has labels), from the image headers alone."""
+    imgs, labels = directory_files(root, path, split)
+    per_pixel = 3 if labels is None else 4
+    return sum(w * h * per_pixel for w, h in _stored_sizes(imgs, store_res, decode_threads()))
+
+
 class DeviceImageStore:
     """Every crop of `{root}/cropped/{dataset}_{crop_type}_crop_{ratio}/{img,label}/{split}` decoded once (PIL, .convert("RGB") for
     the images, the label PNG's bytes as they are) and kept on `device`: `images` uint8 [sum h*w*3] (HWC RGB per crop) and `labels`
@@ -143,6 +165,66 @@ class DeviceImageStore:
         self.lut = torch.from_numpy(normalize_lut()).to(self.device)
         self._tables = {}
 
+    kind, store_res = "cropped", None       # from_directory: "directory", and the one R a reduced store serves
+
+    @classmethod
+    def from_directory(cls, root, path, split, device=None, max_bytes=DEFAULT_MAX_BYTES, store_res=None):
+        """The store of a data.DirectoryDataset split, `{root}/{path}/imgs/{split}/*` and, when `{root}/{path}/labels` exists,
+        `{root}/{path}/labels/{split}/*`: the same two arenas and record table, `labels` None when the folder has none.  `prepare`
+        then goes through stego_data_prepare_dir: label = the stored byte (-1 without labels), mask float32 = label > 0.
+
+        store_res = R: every decoded image and label whose short side is above R is reduced on the host with data._resize(im, R)
+        (PIL's NEAREST) before the upload - a folder of megapixel photos does not fit the device at full size; smaller images are
+        kept as they are (the store never grows).  resized_size leaves an image whose short side already is R alone, so
+        prepare(index, R) is still bitwise the transform of the original file, for centre and random crops alike; such a store
+        serves that R only (table / prepare raise ValueError for another one)."""
+        self = cls.__new__(cls)
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.split, self.kind, self.store_res = split, "directory", None if store_res is None else int(store_res)
+        if self.store_res is not None and not 1 <= self.store_res <= capi.DATA_MAX_RES:
+            raise ValueError("store_res = %d outside [1, %d] (include/stego_data.h)" % (self.store_res, capi.DATA_MAX_RES))
+        imgs, labs = directory_files(root, path, split)
+        threads = decode_threads()
+        sizes = _stored_sizes(imgs, self.store_res, threads)
+        self.w = np.array([s[0] for s in sizes], dtype=np.int64)
+        self.h = np.array([s[1] for s in sizes], dtype=np.int64)
+        npx = self.h * self.w
+        total = int(npx.sum())
+        self.nbytes = total * (3 if labs is None else 4)
+        if self.nbytes > max_bytes:
+            raise StoreTooLarge("the %s split of %s needs %.2f GB on the device (%d images%s) and the budget is %.2f GB"
+                                % (split, join(root, path), self.nbytes / 1e9, len(imgs),
+                                   "" if self.store_res is None else ", reduced to store_res = %d" % self.store_res, max_bytes / 1e9))
+        self.label_offsets = np.concatenate([[0], np.cumsum(npx)[:-1]]).astype(np.int64)
+        self.img_offsets = self.label_offsets * 3
+        host_img = np.empty(total * 3, dtype=np.uint8)
+        host_lab = None if labs is None else np.empty(total, dtype=np.uint8)
+
+        def decode(i):
+            h, w = int(self.h[i]), int(self.w[i])
+            o = int(self.label_offsets[i])
+            with Image.open(imgs[i]) as im:
+                im = im.convert("RGB")
+                rgb = np.asarray(_reduce(im, self.store_res), dtype=np.uint8)
+            if rgb.shape != (h, w, 3):
+                raise ValueError("%s: decoded to %s, its header said %d x %d" % (imgs[i], rgb.shape, w, h))
+            host_img[3 * o:3 * (o + h * w)] = rgb.reshape(-1)
+            if labs is not None:
+                lab = np.asarray(_reduce(open_label(labs[i]), self.store_res))
+                if lab.dtype != np.uint8 or lab.shape != (h, w):
+                    raise ValueError("%s: expected a %d x %d 8-bit label image for %s, got %s %s"
+                                     % (labs[i], w, h, imgs[i], lab.dtype, lab.shape))
+                host_lab[o:o + h * w] = lab.reshape(-1)
+
+        with ThreadPoolExecutor(threads) as ex:
+            list(ex.map(decode, range(len(imgs))))
+        self.images = torch.from_numpy(host_img).to(self.device)
+        self.labels = None if labs is None else torch.from_numpy(host_lab).to(self.device)
+        self._label_bytes = total           # what the records' label offsets are checked against, with or without the arena
+        self.lut = torch.from_numpy(normalize_lut()).to(self.device)
+        self._tables = {}
+        return self
+
     def __len__(self):
         return len(self.h)
 
@@ -154,6 +236,8 @@ class DeviceImageStore:
             return t
         if not 1 <= R <= capi.DATA_MAX_RES:
             raise ValueError("resolution R = %d outside [1, %d] (include/stego_data.h)" % (R, capi.DATA_MAX_RES))
+        if self.store_res is not None and R != self.store_res:
+            raise ValueError("this store was reduced to store_res = %d and serves that resolution only, not R = %d" % (self.store_res, R))
         n = len(self)
         rec = np.zeros(n, dtype=ITEM_DTYPE)
         pool, where, at = [], {}, 0
@@ -173,7 +257,7 @@ class DeviceImageStore:
             rec[i] = (self.img_offsets[i], self.label_offsets[i], h, w, nh, nw, map_of(h, nh), map_of(w, nw),
                       int(round((nh - R) / 2.0)), int(round((nw - R) / 2.0)))
         maps = np.concatenate(pool).astype(np.int32)
-        desc = (R, n, self.images.numel(), self.labels.numel(), len(maps))
+        desc = (R, n, self.images.numel(), self.labels.numel() if self.labels is not None else self._label_bytes, len(maps))
         rc, bad = capi.data_check_items(capi.data_desc(1, *desc), rec)
         if rc != 0:
             raise ValueError("record %d of the %s split is invalid at R = %d: %s (error %d)"
@@ -186,7 +270,7 @@ class DeviceImageStore:
 
     def prepare(self, index, R, origin=None, validate=False):
         """One launch: index int64 [N] (device) -> img float32 [N,3,R,R], label int64 [N,R,R] (stored value - 1), mask bool [N,1,R,R]
-        (label == -1).  origin: int32 [N, 2] (top, left) in resized coordinates, or None for centre crops.  validate=True checks the
+        (label == -1); on a from_directory store label = the stored value (-1 without labels) and mask float32 (label > 0).  origin: int32 [N, 2] (top, left) in resized coordinates, or None for centre crops.  validate=True checks the
         indices and origins on the host first (a device -> host copy) and raises ValueError with the offending value."""
         t = self.table(R)
         index = index.to(self.device, torch.int64).contiguous()
@@ -208,6 +292,8 @@ class DeviceImageStore:
                     k = bad[0]
                     raise ValueError("crop origin %s of item %d (resized %d x %d) does not fit R = %d"
                                      % (tuple(o[k]), ind[k], rec["nh"][k], rec["nw"][k], R))
+        if self.kind == "directory":
+            return capi.data_prepare_dir(t["desc"], t["items"], self.images, self.labels, t["maps"], self.lut, index, origin)
         return capi.data_prepare(t["desc"], t["items"], self.images, self.labels, t["maps"], self.lut, index, origin)
 
 

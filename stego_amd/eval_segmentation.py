@@ -10,7 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from .crf import batched_crf, dense_crf_batch, image_to_bgr_u8
-from .data import _MEAN, _STD, CroppedDataset, _resize_center_crop, crop_dir, image_transform, label_transform  # noqa: F401
+from .data import _MEAN, _STD, CroppedDataset, DirectoryDataset, _resize_center_crop, crop_dir, image_transform, label_transform  # noqa: F401
 from .train_segmentation import LitUnsupervisedSegmenter, SyntheticContrastiveDataset, load_config
 
 EVAL_CONFIG = join(dirname(__file__), "configs", "eval_config.yml")
@@ -94,11 +94,19 @@ def evaluate(model, loader, run_crf=True, device=None, fused_head=False, native_
 
 
 def make_loader(cfg, model):
-    """The val split of the cropped tree under cfg.pytorch_data_dir when it exists (crop_datasets.py's layout), else synthetic data."""
+    """The val split of the cropped tree under cfg.pytorch_data_dir when it exists (crop_datasets.py's layout); for a checkpoint
+    trained on an image folder (dataset_name "directory") that folder's val split when it has labels; else synthetic data."""
     mcfg = model.cfg
     root = getattr(cfg, "pytorch_data_dir", None)
     crop_type, crop_ratio = getattr(mcfg, "crop_type", "five"), getattr(mcfg, "crop_ratio", 0.5)
-    if root and exists(join(crop_dir(root, mcfg.dataset_name, crop_type, crop_ratio), "img", "val")):
+    name = getattr(mcfg, "dir_dataset_name", None)
+    if root and mcfg.dataset_name == "directory" and name and exists(join(root, name, "imgs", "val")) and \
+            exists(join(root, name, "labels", "val")):
+        ds = DirectoryDataset(root, name, "val", transform=image_transform(cfg.res), target_transform=label_transform(cfg.res))
+    elif root and mcfg.dataset_name == "directory":
+        print("no labelled val split of the folder %r under %r: synthetic data" % (name, root))
+        ds = SyntheticContrastiveDataset(cfg.batch_size * 4, cfg.res, model.n_classes, seed=0)
+    elif root and exists(join(crop_dir(root, mcfg.dataset_name, crop_type, crop_ratio), "img", "val")):
         ds = CroppedDataset(root, mcfg.dataset_name, crop_type, crop_ratio, "val", transform=image_transform(cfg.res),
                             target_transform=label_transform(cfg.res))
     else:

@@ -246,6 +246,15 @@ def _device_generator(dev):
     return torch.cuda.default_generators[dev.index if dev.index is not None else torch.cuda.current_device()]
 
 
+def _native_salience_covers(m1, m2, B, S):
+    """Can stego_salience_coords take these masks (include/stego_salience.h: [B, H, W] uint8 / bool / float32, its size limits)?"""
+    if m1 is None or m2 is None or m1.dim() != 3 or m1.shape != m2.shape or m1.dtype != m2.dtype or m1.shape[0] != B:
+        return False
+    if m1.dtype not in (torch.float32, torch.uint8, torch.bool) or not (m1.is_cuda and m2.is_cuda):
+        return False
+    return capi.salience_covers(B, int(m1.shape[1]), int(m1.shape[2]), int(S))
+
+
 def _torch_draws(shape, n, B, dev):
     """The reference's draws as the reference makes them (modules.py:366-367, :383): seven torch calls on the device generator."""
     out = [torch.rand(shape, device=dev), torch.rand(shape, device=dev)]
@@ -1046,6 +1055,20 @@ class ContrastiveCorrelationLoss(nn.Module):
             n = cfg.neg_samples
             out = _torch_draws(shape, n, B, dev)
             coords1, coords2, perms = _backend.finish_draws(out[0], out[1], out[2:], B)
+            if n == 0:
+                perms = None
+        elif dev.type == "cuda" and cfg.use_salience and getattr(cfg, "native_salience", False) and \
+                hasattr(_backend, "salience_coords") and _native_salience_covers(orig_salience, orig_salience_pos, B, cfg.feature_samples):
+            # OPT-IN (cfg.native_salience, default off): sample_nonzero_locations x 2 - torch.nonzero and a Python loop over the batch
+            # with a host randint per image, 2 * B host synchronisations - as ONE launch (include/stego_salience.h) fed by uniform
+            # numbers of the device generator: the same distribution, not the torch path's random stream.  No host synchronisation:
+            # the step can be captured in a HIP graph.
+            S, n = cfg.feature_samples, cfg.neg_samples
+            out = _torch_draws([B, S, S, 2], n, B, dev)
+            u = torch.rand([2, B, S, S, 3], device=dev)
+            u_mix = torch.rand([B, S, S], device=dev)
+            reg1, reg2, perms = _backend.finish_draws(out[0], out[1], out[2:], B)
+            coords1, coords2 = _backend.salience_coords(orig_salience, orig_salience_pos, u, u_mix, reg1, reg2)
             if n == 0:
                 perms = None
         else:

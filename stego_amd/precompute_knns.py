@@ -121,22 +121,47 @@ def _split_loader(cfg, image_set, device):
     from .device_data import DeviceContrastiveLoader, DeviceImageStore, StoreTooLarge
     max_bytes = float(getattr(cfg, "device_dataset_max_gb", 200)) * 2 ** 30
     try:
-        store = DeviceImageStore(cfg.pytorch_data_dir, cfg.dataset_name, cfg.crop_type, cfg.crop_ratio, image_set, device=device,
-                                 max_bytes=max_bytes)
+        if cfg.dataset_name == "directory":
+            # only the centre crops at KNN_RES are read: the store holds every image reduced to that resolution
+            store = DeviceImageStore.from_directory(cfg.pytorch_data_dir, cfg.dir_dataset_name, image_set, device=device,
+                                                    max_bytes=max_bytes, store_res=KNN_RES)
+        else:
+            store = DeviceImageStore(cfg.pytorch_data_dir, cfg.dataset_name, cfg.crop_type, cfg.crop_ratio, image_set, device=device,
+                                     max_bytes=max_bytes)
         return DeviceContrastiveLoader(store, None, batch_size=KNN_BATCH, res=KNN_RES, drop_last=False)
     except StoreTooLarge as e:
         print("%s: reading it on the CPU" % e)
-    ds = ContrastiveSegDataset(cfg.pytorch_data_dir, cfg.dataset_name, cfg.crop_type, image_set, image_transform(KNN_RES),
+    ds = ContrastiveSegDataset(cfg.pytorch_data_dir, cfg.dataset_name, _crop_type(cfg), image_set, image_transform(KNN_RES),
                                label_transform(KNN_RES), cfg)
     return torch.utils.data.DataLoader(ds, KNN_BATCH, shuffle=False, num_workers=getattr(cfg, "num_workers", 0))
 
 
+def _crop_type(cfg):
+    """precompute_knns.py:43-45, :64 - an image folder (dataset_name "directory") has no crops: crop_type None, and the table's name
+    carries cfg.dir_dataset_name and the literal "None"."""
+    return None if cfg.dataset_name == "directory" else cfg.crop_type
+
+
+def nns_path(cfg, image_set, res):
+    """Where the neighbour table of a split lies: {pytorch_data_dir}/nns/nns_filename(...) with the reference's nice_dataset_name."""
+    name = cfg.dir_dataset_name if cfg.dataset_name == "directory" else cfg.dataset_name
+    return join(cfg.pytorch_data_dir, "nns", nns_filename(cfg.model_type, name, image_set, _crop_type(cfg), res))
+
+
+def split_dir(cfg, image_set):
+    """The folder that holds a split's images: the cropped tree's img/{split}, or {dir_dataset_name}/imgs/{split}."""
+    from .data import crop_dir
+    if cfg.dataset_name == "directory":
+        return join(cfg.pytorch_data_dir, cfg.dir_dataset_name, "imgs", image_set)
+    return join(crop_dir(cfg.pytorch_data_dir, cfg.dataset_name, cfg.crop_type, cfg.crop_ratio), "img", image_set)
+
+
 def my_app(cfg):
-    """precompute_knns.py:24-97 for cfg.dataset_name and cfg.crop_type: for the val and train splits of the cropped tree whose table
+    """precompute_knns.py:24-97 for cfg.dataset_name and cfg.crop_type: for the val and train splits of the cropped tree (or, for
+    dataset_name "directory", of the image folder {pytorch_data_dir}/{dir_dataset_name}/imgs) whose table
     {pytorch_data_dir}/nns/nns_filename(...) does not exist yet, the mean-pooled, L2-normalised backbone features of the centre crops
     at 224 and their 30 nearest neighbours, written with save_nns.  The backbone runs in eval mode (the reference leaves the
     featurizer's feature dropout on).  Returns the paths written."""
-    from .data import crop_dir
     pytorch_data_dir = cfg.pytorch_data_dir
     os.makedirs(join(cfg.output_root, "data"), exist_ok=True)
     os.makedirs(join(cfg.output_root, "logs"), exist_ok=True)
@@ -148,12 +173,13 @@ def my_app(cfg):
     model = None
     written = []
     for image_set in ["val", "train"]:
-        path = join(pytorch_data_dir, "nns", nns_filename(cfg.model_type, cfg.dataset_name, image_set, cfg.crop_type, KNN_RES))
+        path = nns_path(cfg, image_set, KNN_RES)
         if exists(path):
             print("{} exists, skipping".format(path))
             continue
-        if not exists(join(crop_dir(pytorch_data_dir, cfg.dataset_name, cfg.crop_type, cfg.crop_ratio), "img", image_set)):
-            print("no cropped {} split under {}: nothing to compute".format(image_set, pytorch_data_dir))
+        if not exists(split_dir(cfg, image_set)):
+            print("no {} {} split under {}: nothing to compute".format("directory" if cfg.dataset_name == "directory" else "cropped",
+                                                                       image_set, pytorch_data_dir))
             continue
         print("{} not found, computing".format(path))
         if model is None:
@@ -161,7 +187,9 @@ def my_app(cfg):
         with torch.no_grad():
             normed_feats = get_feats(model, _split_loader(cfg, image_set, device), device=device)
             print(tuple(normed_feats.shape))
-            nearest_neighbors = compute_nearest_neighbors(normed_feats, k=30)
+            # a user's folder may hold fewer than 30 images (the cropped trees never do): then every image is a neighbour
+            k = min(30, normed_feats.shape[0]) if cfg.dataset_name == "directory" else 30
+            nearest_neighbors = compute_nearest_neighbors(normed_feats, k=k)
         save_nns(path, nearest_neighbors)
         print("Saved NNs", cfg.model_type, cfg.dataset_name, image_set)
         written.append(path)

@@ -587,14 +587,86 @@ def _real_loaders(cfg, trainer):
     return loader, val_loader
 
 
+def _directory_loaders(cfg, trainer):
+    """_real_loaders for dataset_name "directory" (the image folder {pytorch_data_dir}/{dir_dataset_name}, data.DirectoryDataset).
+    The training loader is, in this order: the device store at full size when it fits cfg.device_dataset_max_gb; else the device store
+    reduced to store_res = cfg.res (bitwise the same batches); else ContrastiveSegDataset on cfg.num_workers CPU workers.  Validation
+    (centre crops at 320) runs only when the folder has both imgs/val and labels/val."""
+    import numpy as np
+    from .data import ContrastiveSegDataset, image_transform, label_transform
+    from .device_data import DeviceContrastiveLoader, DeviceImageStore, StoreTooLarge
+    from .precompute_knns import nns_path
+    root, name = cfg.pytorch_data_dir, cfg.dir_dataset_name
+    crop = getattr(cfg, "loader_crop_type", "center")
+    max_gb = getattr(cfg, "device_dataset_max_gb", 200)
+    max_bytes = float(max_gb) * 2 ** 30
+    table = nns_path(cfg, "train", cfg.res)
+    if not os.path.exists(join(root, name, "labels")):
+        print("training data: %s has no labels folder: every label is -1, so loss/linear and loss/total are NaN (no valid pixel: NaN "
+              "loss, zero gradients, as F.cross_entropy gives the reference); every gradient stays finite and the cluster probe and "
+              "the correspondence losses train as usual" % join(root, name))
+    loader = None
+    if getattr(cfg, "device_dataset", True):
+        store = None
+        try:
+            store = DeviceImageStore.from_directory(root, name, "train", device=trainer.device, max_bytes=max_bytes)
+            print("training data: device store of the folder at full size (%d images, %.2f GB on the device)" % (len(store), store.nbytes / 1e9))
+        except StoreTooLarge as e:
+            try:
+                store = DeviceImageStore.from_directory(root, name, "train", device=trainer.device, max_bytes=max_bytes, store_res=cfg.res)
+                print("training data: device store reduced to store_res = %d (%d images, %.2f GB on the device): %s "
+                      "(cfg.device_dataset_max_gb = %s)" % (cfg.res, len(store), store.nbytes / 1e9, e, max_gb))
+            except StoreTooLarge as e2:
+                print("training data: CPU loader (ContrastiveSegDataset, %d workers): %s (cfg.device_dataset_max_gb = %s)"
+                      % (cfg.num_workers, e2, max_gb))
+        if store is not None:
+            if not os.path.exists(table):
+                raise ValueError("could not find nn file {} please run precompute_knns".format(table))
+            loader = DeviceContrastiveLoader(store, np.load(table)["nns"], cfg.batch_size, cfg.num_neighbors, cfg.res, crop=crop,
+                                             seed=0, rank=trainer.rank, world=trainer.world, drop_last=True,
+                                             aug=cfg.aug_alignment_weight > 0 and getattr(cfg, "native_aug", False))
+    else:
+        print("training data: CPU loader (ContrastiveSegDataset, %d workers): cfg.device_dataset is off" % cfg.num_workers)
+    if loader is None:
+        ds = ContrastiveSegDataset(root, "directory", None, "train", image_transform(cfg.res, crop), label_transform(cfg.res, crop), cfg,
+                                   num_neighbors=cfg.num_neighbors, mask=True, pos_images=True, pos_labels=True)
+        loader = torch.utils.data.DataLoader(ds, cfg.batch_size, shuffle=True, num_workers=cfg.num_workers, pin_memory=True,
+                                             drop_last=True)
+    val_loader = None
+    if os.path.exists(join(root, name, "imgs", "val")) and os.path.exists(join(root, name, "labels", "val")):
+        if getattr(cfg, "device_dataset", True):
+            try:
+                vstore = DeviceImageStore.from_directory(root, name, "val", device=trainer.device, max_bytes=max_bytes, store_res=320)
+                val_loader = DeviceContrastiveLoader(vstore, None, cfg.batch_size, res=320, drop_last=False)
+            except StoreTooLarge as e:
+                print("val data: CPU loader: %s" % e)
+        if val_loader is None:
+            vds = ContrastiveSegDataset(root, "directory", None, "val", image_transform(320), label_transform(320), cfg, mask=True)
+            val_loader = torch.utils.data.DataLoader(vds, cfg.batch_size, shuffle=False, num_workers=cfg.num_workers, pin_memory=True)
+    else:
+        print("no labelled val split in the folder: training without validation")
+    return loader, val_loader
+
+
 def my_app(cfg):
     """Trains on the cropped tree {pytorch_data_dir}/cropped/{dataset}_{crop_type}_crop_{ratio} when its train split exists (KNN
-    positives from precompute_knns' table), on synthetic data otherwise.  Returns the per-step losses."""
+    positives from precompute_knns' table), on the image folder {pytorch_data_dir}/{dir_dataset_name} for dataset_name "directory"
+    (n_classes = cfg.dir_dataset_n_classes), on synthetic data otherwise.  Returns the per-step losses."""
     from .data import crop_dir
     torch.manual_seed(0)            # seed_everything(0), train_segmentation.py:403
-    n_classes = get_class_labels(cfg.dataset_name)
     root = getattr(cfg, "pytorch_data_dir", None)
-    if root and os.path.exists(join(crop_dir(root, cfg.dataset_name, cfg.crop_type, cfg.crop_ratio), "img", "train")):
+    if cfg.dataset_name == "directory":
+        n_classes = int(cfg.dir_dataset_n_classes)
+        if not root or not os.path.exists(join(root, cfg.dir_dataset_name, "imgs", "train")):
+            raise ValueError("dataset_name directory: no folder %s" % join(str(root), str(cfg.dir_dataset_name), "imgs", "train"))
+        if getattr(cfg, "loader_crop_type", "center") not in ("center", "random"):
+            raise ValueError("loader_crop_type %r is not supported (center or random)" % cfg.loader_crop_type)
+        real = _directory_loaders
+    else:
+        n_classes = get_class_labels(cfg.dataset_name)
+        real = _real_loaders
+    if cfg.dataset_name == "directory" or \
+            (root and os.path.exists(join(crop_dir(root, cfg.dataset_name, cfg.crop_type, cfg.crop_ratio), "img", "train"))):
         refusal = needs_torchvision(cfg)
         if refusal:
             raise ValueError(refusal)
@@ -605,7 +677,7 @@ def my_app(cfg):
         ckpt = checkpoint_path(cfg)
         os.makedirs(dirname(ckpt), exist_ok=True)
         trainer = Trainer(cfg.max_steps, log_every=cfg.scalar_log_freq, val_check_interval=cfg.val_freq, checkpoint_path=ckpt)
-        loader, trainer.val_loader = _real_loaders(cfg, trainer)
+        loader, trainer.val_loader = real(cfg, trainer)
         model = LitUnsupervisedSegmenter(n_classes, cfg)
         return trainer.fit(model, loader)
     trainer = Trainer(cfg.max_steps)

@@ -2,6 +2,7 @@
 cached-token training step fed by each.  Prints one JSON line.
 
     python tools/bench_data.py [--sources 80] [--steps 40] [--cpu-workers 16]
+    python tools/bench_data.py --directory      # stego_data_prepare_dir against stego_data_prepare -> profiles/data_dir_bench.json
 
 The tree: `--sources` smooth random 640 x 480 images written with data.write_cropped (five 320 x 240 crops each) under a temporary
 directory, and a random neighbour table.  Kernel times are CUDA-event means over back-to-back launches into preallocated outputs;
@@ -46,29 +47,54 @@ def make_tree(root, n_src, seed=0):
     return n, nns
 
 
-def time_kernel(store, n_items, R=224, iters=200):
+def time_kernel(store, n_items, R=224, iters=200, directory=False):
+    """directory=True: stego_data_prepare_dir (float32 mask, 24 output bytes per pixel) on the same arenas and records."""
     dev = store.device
     t = store.table(R)
     ind = torch.randint(0, len(store), (n_items,), device=dev, generator=torch.Generator(device=dev).manual_seed(1))
     img = torch.empty(n_items, 3, R, R, device=dev)
     label = torch.empty(n_items, R, R, dtype=torch.int64, device=dev)
-    mask = torch.empty(n_items, 1, R, R, dtype=torch.bool, device=dev)
+    mask = torch.empty(n_items, 1, R, R, dtype=torch.float32 if directory else torch.bool, device=dev)
     desc = capi.data_desc(n_items, *t["desc"])
     args = (desc, t["items"], store.images, store.labels, t["maps"], store.lut, ind, None, img, label, mask)
+    run = capi.data_prepare_dir_raw if directory else capi.data_prepare_raw
+    out_bytes = 24.0 if directory else 21.0
     for _ in range(10):
-        assert capi.data_prepare_raw(*args) == 0
+        assert run(*args) == 0
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(iters):
-        capi.data_prepare_raw(*args)
+        run(*args)
     e1.record()
     torch.cuda.synchronize()
     us = e0.elapsed_time(e1) * 1e3 / iters
     rec = t["records"][ind.cpu().numpy()]
     src = float((rec["h"].astype(np.int64) * rec["w"] * 4).sum())      # upper bound: every source byte of the items read once
-    nbytes = 21.0 * R * R * n_items + min(src, 4.0 * R * R * n_items)
-    return dict(items=n_items, R=R, us=round(us, 2), out_mb=round(21.0 * R * R * n_items / 1e6, 2),
+    nbytes = out_bytes * R * R * n_items + min(src, 4.0 * R * R * n_items)
+    return dict(items=n_items, R=R, us=round(us, 2), out_mb=round(out_bytes * R * R * n_items / 1e6, 2),
                 roofline_frac=round(nbytes / (us * 1e-6) / HBM_BYTES_PER_S, 3))
+
+
+def directory_main(a):
+    """--directory: stego_data_prepare_dir against stego_data_prepare on the same arenas, records and indices in one process, each
+    timed twice in alternation (the order of two back-to-back measurements can matter) -> profiles/data_dir_bench.json."""
+    dev = torch.device("cuda", 0)
+    with tempfile.TemporaryDirectory() as root:
+        n, _ = make_tree(root, a.sources)
+        store = DD.DeviceImageStore(root, "cocostuff27", "five", 0.5, "train", device=dev)
+    rows = []
+    for b in (16, 32):
+        runs = [(time_kernel(store, 2 * b), time_kernel(store, 2 * b, directory=True)) for _ in range(2)]
+        base, dirs = min(r[0]["us"] for r in runs), min(r[1]["us"] for r in runs)
+        rows.append(dict(items=2 * b, R=224, prepare_us=[r[0]["us"] for r in runs], prepare_dir_us=[r[1]["us"] for r in runs],
+                         ratio_of_best=round(dirs / base, 3), output_bytes_ratio=round(24 / 21, 3),
+                         prepare_dir_roofline_frac=max(r[1]["roofline_frac"] for r in runs)))
+    result = dict(tool="bench_data --directory", crops=n, crop_hw=[240, 320], rows=rows)
+    out = join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "data_dir_bench.json")
+    with open(out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print(json.dumps(result))
 
 
 def loader_rate(it, n_batches, sync):
@@ -110,7 +136,10 @@ def main():
     ap.add_argument("--sources", type=int, default=80)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--cpu-workers", type=int, default=16)
+    ap.add_argument("--directory", action="store_true", help="time stego_data_prepare_dir against stego_data_prepare on the same bytes")
     a = ap.parse_args()
+    if a.directory:
+        return directory_main(a)
     dev = torch.device("cuda", 0)
     with tempfile.TemporaryDirectory() as root:
         n, nns = make_tree(root, a.sources)
