@@ -11,7 +11,8 @@
  *     K_g: (x / pos_xy_std, y / pos_xy_std)                              d = 2
  *     K_b: (x / bi_xy_std, y / bi_xy_std, B / bi_rgb_std, G / bi_rgb_std, R / bi_rgb_std)     d = 5
  * csrc/dense_crf.hip has the construction (embedding, sort, vertices, neighbours) and the per-iteration kernels.  The result is
- * bitwise identical run to run (no float atomics, no hash table).
+ * bitwise identical run to run (no float atomics, no hash table).  Arithmetic is fp32 but for the softmax over c and the log of the
+ * unary, which are evaluated in double and rounded once (the mean-field multiplies what each iteration's rounding adds).
  *
  * Conventions as in stego_corr.h: device pointers, nothing allocated / freed / synchronised, work enqueued on `stream`, STEGO_OK or
  * an error code.

@@ -17,7 +17,9 @@
 //   crf_blur_kernel        d+1 ping-pong passes v' = v + (v[n1] + v[n2]) / 2 over [M, C_pad] rows; the first pass adds up each
 //                          vertex's pieces as it reads it
 //   crf_combine_kernel     per pixel: slice both lattices, -U + pos_w K_g + bi_w K_b, softmax over C (group shuffles); writes the next
-//                          s_g * Q and s_b * Q, and Q itself ([B, C, H, W]) after the last iteration
+//                          s_g * Q and s_b * Q, and Q itself ([B, C, H, W]) after the last iteration.  Once before the loop
+//                          with `first` set: Q0 = softmax(-U) of what crf_unary_kernel wrote
+// The softmax and the unary's log are evaluated in double and rounded once; everything else is fp32 in the oracle's order.
 // No float atomics and no order that depends on scheduling: the result is bitwise identical run to run.
 #pragma clang fp contract(off)
 
@@ -401,14 +403,17 @@ __device__ inline float group_max(float v)
 }
 
 template <int G>
-__device__ inline float group_sum(float v)
+__device__ inline double group_sum(double v)
 {
 #pragma unroll
     for (int m = 1; m < G; m <<= 1) v += __shfl_xor(v, m, 64);
     return v;
 }
 
-// softmax over the C valid channels of a pixel held by G lanes (channel 4 lane + t); invalid channels come out 0
+// softmax over the C valid channels of a pixel held by G lanes (channel 4 lane + t); invalid channels come out 0.  Evaluated in
+// double on the float logits and rounded once: Q is the correctly rounded softmax of its input, whatever the group width and
+// the order of the sum.  expf's ulp, the float sum and the float division were the kernels' largest rounding per iteration, and
+// the mean-field multiplies what each iteration adds (about 2 x per iteration on colour noise)
 template <int G>
 __device__ inline float4 group_softmax(float4 x, int lane, int C)
 {
@@ -418,14 +423,14 @@ __device__ inline float4 group_softmax(float4 x, int lane, int C)
     for (int t = 0; t < 4; ++t)
         if (4 * lane + t < C) m = fmaxf(m, v[t]);
     m = group_max<G>(m);
-    float e[4], s = 0.f;
+    double e[4], s = 0.0;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-        e[t] = (4 * lane + t < C) ? expf(v[t] - m) : 0.f;
+        e[t] = (4 * lane + t < C) ? exp((double)v[t] - (double)m) : 0.0;
         s += e[t];
     }
     s = group_sum<G>(s);
-    return make_float4(e[0] / s, e[1] / s, e[2] / s, e[3] / s);
+    return make_float4((float)(e[0] / s), (float)(e[1] / s), (float)(e[2] / s), (float)(e[3] / s));
 }
 
 struct CombineParams {
@@ -433,6 +438,7 @@ struct CombineParams {
     Pix px;
     size_t og_fin, ob_fin;   // where the last blur pass of each lattice wrote
     int N, C, cq;
+    int first;               // crf_combine_kernel: Q0 = softmax(-U), no lattice is read
     float pos_w, bi_w;
     float* q_out;            // [B, C, H, W], written when not NULL
     const float* probs;      // crf_unary_kernel: [B, C, H, W]
@@ -471,7 +477,8 @@ __device__ inline void store_state(const CombineParams& p, int b, int k, int lan
     }
 }
 
-// -U = log(clip(p, 1e-5, 1)) and Q0 = softmax(-U)
+// -U = log(clip(p, 1e-5, 1)), the log in double and rounded once.  Q0 = softmax(-U) is the combine kernel's, with p.first set: the
+// double log and the double softmax in one kernel would not fit 8 waves per SIMD
 template <int G>
 __global__ __launch_bounds__(TPB) void crf_unary_kernel(CombineParams p)
 {
@@ -482,11 +489,10 @@ __global__ __launch_bounds__(TPB) void crf_unary_kernel(CombineParams p)
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const int c = 4 * lane + t;
-            v[t] = c < p.C ? logf(fminf(fmaxf(p.probs[((size_t)b * p.C + c) * p.N + k], 1e-5f), 1.0f)) : 0.f;
+            v[t] = c < p.C ? (float)log((double)fminf(fmaxf(p.probs[((size_t)b * p.C + c) * p.N + k], 1e-5f), 1.0f)) : 0.f;     // rounded once
         }
         const float4 nu = make_float4(v[0], v[1], v[2], v[3]);
         if (lane < p.cq) at<float4>(p.px, p.px.o_negu, b)[(size_t)k * p.cq + lane] = nu;
-        store_state<G>(p, b, k, lane, group_softmax<G>(nu, lane, p.C));
     }
 }
 
@@ -497,7 +503,9 @@ __global__ __launch_bounds__(TPB) void crf_combine_kernel(CombineParams p)
     const int ngrp = gridDim.x * (TPB / G);
     for (int k = blockIdx.x * (TPB / G) + threadIdx.x / G; k < p.N; k += ngrp) {
         float4 x = f4(0.f);
-        if (lane < p.cq) {
+        if (lane < p.cq && p.first) {
+            x = at<float4>(p.px, p.px.o_negu, b)[(size_t)k * p.cq + lane];
+        } else if (lane < p.cq) {
             const float sg = at<float>(p.g, p.g.o_s, b)[k], sb = at<float>(p.bl, p.bl.o_s, b)[k];
             const float4 kg = mul(sg, slice<2>(p.g, p.og_fin, b, k, p.cq, lane));
             const float4 kb = mul(sb, slice<5>(p.bl, p.ob_fin, b, k, p.cq, lane));
@@ -704,6 +712,9 @@ int iterate(const StegoCrfDesc* d, const Geom& g, char* ws, const float* probs, 
     p.q_out = d->n_iter == 0 ? q_out : nullptr;
     const dim3 gp = grid((size_t)g.N, TPB / G, B);
     crf_unary_kernel<G><<<gp, TPB, 0, st>>>(p);
+    p.first = 1;
+    crf_combine_kernel<G><<<gp, TPB, 0, st>>>(p);
+    p.first = 0;
     const char* sqg = g.pix.base + g.pix.o_sqg;
     const char* sqb = g.pix.base + g.pix.o_sqb;
     for (int it = 0; it < d->n_iter; ++it) {
