@@ -32,6 +32,7 @@
 #include "host_util.h"
 #include "../../include/stego_corr.h"
 #include "corr_wide.h"
+#include "corr_wide_plan.h"
 #include "launchers.h"
 
 namespace stego {
@@ -140,8 +141,8 @@ __global__ void __launch_bounds__(1024) wide_loss_means_kernel(const WidePwParam
 // ------------------------------------------------------------------------------------------------ backward: both adjoints of the code correlation
 constexpr int WB_GS = 132;      // floats per row of the G tile (528 B: conflict-free 16-byte reads along a row, column walks hit 64 banks)
 constexpr int WB_TS = 136;      // halves per row of a transposed code tile [channel][128 points] (272 B: conflict-free 16-byte reads)
-constexpr int WB_MAXNB = 2;     // point blocks per side: S * S <= 256
-constexpr int WB_MAXKB = 3;     // 32-channel blocks of one pass: <= 88 channels (the tiles of both sides + G in 160 KB of LDS); K <= 128 in two passes
+// (WB_MAXNB = 2 point blocks per side, WB_MAXKB = 3 32-channel blocks of one pass - <= 88 channels: the tiles of both sides + G in 160 KB of
+// LDS; K <= 128 in two passes: corr_wide_plan.h)
 
 struct WideBwdParams {
     const float* w;             // saved_w [n_img][P][P]
@@ -290,6 +291,7 @@ __device__ __forceinline__ void wide_build_lists(const WideGatherParams& p, int 
 // TRANSPOSED ([channel][point]: a fragment of either product is then 8 consecutive points of one channel = one 16-byte LDS read) and split
 // into fp16 hi | lo, in the layout the GEMM kernel keeps in LDS - staging a tile there is a linear LDS-DMA copy.
 constexpr int WB_ZERO_CHUNK = 16384;      // floats per zeroing workgroup
+static_assert(WIDE_LIST_THREADS == 512, "the list builders are workgroups of the code-tile launch");
 __global__ void __launch_bounds__(512) wide_code_tiles_kernel(const WideBwdParams p, const WideGatherParams q, const int list_blocks)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -300,7 +302,7 @@ __global__ void __launch_bounds__(512) wide_code_tiles_kernel(const WideBwdParam
     if ((int)blockIdx.x >= n_tiles && (int)blockIdx.x < n_tiles + list_blocks) {
         // the lists of the pixel gather (they depend on the coordinates and permutations only: built here, beside the tiles, in front of the GEMMs)
         const int lb = blockIdx.x - n_tiles;
-        wide_build_lists<512>(q, lb / q.B, lb % q.B, smem);
+        wide_build_lists<WIDE_LIST_THREADS>(q, lb / q.B, lb % q.B, smem);
         return;
     }
     if ((int)blockIdx.x >= n_tiles) {
@@ -564,7 +566,7 @@ __global__ void __launch_bounds__(WB_THREADS) wide_bwd_kernel(const WideBwdParam
 //                            first-operand gradients of all pair-sets summed in)
 //   wide_gather_kernel       one wave per pixel: its <= 64 entries sorted by key (so that the sum has one order whatever order the fill took),
 //                            then out[pixel][:] = sum w * V[row][:], K floats per entry in one or two coalesced loads.  A pixel with more than 64
-//                            taps is summed chunk by chunk (order of the chunks as filled)
+//                            taps is summed group by group of 64 consecutive rows, each sorted likewise: one order as well
 // Against the one-wave-per-point scatter with global fp32 atomics (88 us for three launches at S = 16, 52 us of them the atomics).
 __global__ void __launch_bounds__(256) wide_rows_kernel(const WideGatherParams p)
 {
@@ -613,12 +615,9 @@ __global__ void __launch_bounds__(256) wide_gather_kernel(const WideGatherParams
     const int* goff = p.off + (size_t)wm * (HW + 1);
     const int beg = goff[pix], end = goff[pix + 1];
     float a0 = 0.f, a1 = 0.f;
-    for (int b0 = beg; b0 < end; b0 += 64) {
-        const int n = min(64, end - b0);
-        unsigned key = 0xffffffffu;
-        float w = 0.f;
-        if (lane < n) { key = p.ent[2 * (size_t)(b0 + lane)]; w = __builtin_bit_cast(float, p.ent[2 * (size_t)(b0 + lane) + 1]); }
-        // sort the chunk by key: rank = entries with a smaller key (keys are distinct), then every lane sends its entry to lane `rank`
+    // adds the n <= 64 entries the lanes [0, n) hold, in key order
+    auto add_sorted = [&](unsigned key, float w, int n) {
+        // sort by key: rank = entries with a smaller key (keys are distinct), then every lane sends its entry to lane `rank`
         int rank = 0;
         for (int i = 0; i < n; ++i) rank += (unsigned)__builtin_amdgcn_readlane((int)key, i) < key ? 1 : 0;
         const unsigned skey = (unsigned)__builtin_amdgcn_ds_permute(rank << 2, (int)key);
@@ -644,6 +643,51 @@ __global__ void __launch_bounds__(256) wide_gather_kernel(const WideGatherParams
             a0 = __builtin_fmaf(wi, lane < K ? vr[lane] : 0.f, a0);
             if (lane + 64 < K) a1 = __builtin_fmaf(wi, vr[lane + 64], a1);
         }
+    };
+    if (end - beg <= 64) {
+        unsigned key = 0xffffffffu;
+        float w = 0.f;
+        if (lane < end - beg) { key = p.ent[2 * (size_t)(beg + lane)]; w = __builtin_bit_cast(float, p.ent[2 * (size_t)(beg + lane) + 1]); }
+        add_sorted(key, w, end - beg);
+    } else {
+        // A crowded pixel.  Its list lies in the order the fill's atomics took, so chunks of 64 LIST POSITIONS would hold other entries, and
+        // the sum other last bits, from one launch to the next.  The chunks are therefore made of the keys: the entries of 64 consecutive rows
+        // (key >> 8), groups in ascending order.  A group holds at most 64 entries of one pixel - the taps of a point that carry a weight lie
+        // on different pixels (make_taps zeroes the taps it folds onto their neighbours, and the list builder drops them).  Two passes over
+        // the list per group that exists
+        int last = -1;
+        for (;;) {
+            unsigned next = 0xffffffffu;
+            for (int b0 = beg; b0 < end; b0 += 64) {
+                if (b0 + lane < end) {
+                    const unsigned g = p.ent[2 * (size_t)(b0 + lane)] >> 8;
+                    if ((int)g > last && g < next) next = g;
+                }
+            }
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) next = min(next, (unsigned)__shfl_xor((int)next, m, 64));
+            next = (unsigned)__builtin_amdgcn_readfirstlane((int)next);
+            if (next == 0xffffffffu) break;
+            unsigned key = 0xffffffffu;
+            float w = 0.f;
+            int cnt = 0;
+            for (int b0 = beg; b0 < end; b0 += 64) {
+                unsigned k = 0xffffffffu, wb = 0u;
+                if (b0 + lane < end) { k = p.ent[2 * (size_t)(b0 + lane)]; wb = p.ent[2 * (size_t)(b0 + lane) + 1]; }
+                const bool hit = (k >> 8) == next;              // (no key reaches 0xffffff00: 4 n_img P < 2^31, wide_supported_shape)
+                const unsigned long long mask = __ballot(hit);
+                if (mask == 0ull) continue;
+                // the hits move to the lanes [cnt, cnt + h), in list order; the other lanes send theirs to the lanes that are left (a permutation)
+                const int h = __popcll(mask), pre = lane_prefix(mask);
+                const int dest = (hit ? cnt + pre : cnt + h + (lane - pre)) & 63;
+                const unsigned tk = (unsigned)__builtin_amdgcn_ds_permute(dest << 2, (int)k);
+                const unsigned tw = (unsigned)__builtin_amdgcn_ds_permute(dest << 2, (int)wb);
+                if (lane >= cnt && lane < cnt + h) { key = tk; w = __builtin_bit_cast(float, tw); }
+                cnt += h;
+            }
+            add_sorted(key, w, min(cnt, 64));
+            last = (int)next;
+        }
     }
     const int which = wm / p.B, m = wm - which * p.B;
     float* o = p.d_map[which] + ((size_t)m * HW + pix) * K;
@@ -654,9 +698,7 @@ __global__ void __launch_bounds__(256) wide_gather_kernel(const WideGatherParams
 // ------------------------------------------------------------------------------------------------ host side
 bool wide_supported(int B, int C, int K, int S, int n_neg)
 {
-    const int P = S * S;
-    return P > TP && P <= WB_MAXNB * TP && K <= 128 && B >= 1 && C >= 1 && n_neg >= 0 &&
-           (long long)(2 + n_neg) * B <= 65535 && (long long)(2 + n_neg) * B * P < (1ll << 31) / 4;
+    return wide_supported_shape(B, C, K, S, n_neg);
 }
 
 static size_t up256(size_t v) { return (v + 255) / 256 * 256; }
@@ -669,8 +711,9 @@ WideGeom wide_geometry(int B, int C, int K, int H, int W, int S, int n_neg)
     g.P = S * S;
     g.nb = (g.P + TP - 1) / TP;
     // the backward's GEMM kernel takes the code channels in windows of <= 88 (its LDS): one pass up to K = 88, two beyond
-    g.nwin = (K + 87) / 88;
-    g.Kc = (((K + g.nwin - 1) / g.nwin) + 7) & ~7;
+    const WideWindows win = wide_windows(K);
+    g.nwin = win.nwin;
+    g.Kc = win.Kc;
     g.Kr = g.Kc;
     g.fimg = dense_panel_image_bytes(C, g.P);
     g.cimg = dense_panel_image_bytes(K, g.P);
@@ -774,8 +817,7 @@ hipError_t launch_wide_bwd(const WideBwdArgs& a, hipStream_t stream)
     const int HW = a.H * a.W;
     // (debug bit 20: the scatter with global atomics.  ADVICE round 5: the list builder keeps 2 HW + n_neg B + ... words in LDS - beyond the
     // 160 KB a shape that the forward took must not fail here: it takes the scatter path)
-    const bool gather = HW <= 4096 && (size_t)(2 * HW + 1 + nnb + 2 + 512 / 64 + 4) * 4 <= (size_t)160 * 1024 - 1024 &&
-                        !(knob(KNOB_DEBUG_BWD) & (1 << 20));
+    const bool gather = wide_gather(B, a.H, a.W, a.n_neg, knob(KNOB_DEBUG_BWD));
     WideGatherParams q{};
     q.d_rows = p.d_rows; q.d_anchor = p.d_anchor; q.cn = cn; q.inv = inv; q.co1 = co1; q.co2 = co2; q.perms = a.perms;
     q.V = reinterpret_cast<float*>(ws + g.b_v);
@@ -784,7 +826,7 @@ hipError_t launch_wide_bwd(const WideBwdArgs& a, hipStream_t stream)
     q.d_map[0] = a.d_code; q.d_map[1] = a.d_code_pos;
     q.B = B; q.P = P; q.S = a.S; q.K = K; q.H = a.H; q.W = a.W; q.n_sets = g.n_sets; q.n_neg = a.n_neg;
     const int list_blocks = gather ? 2 * B : 0;
-    const int lds_lists = (2 * HW + 1 + nnb + 2 + 512 / 64 + 4) * 4;
+    const int lds_lists = gather ? (int)wide_list_lds_bytes(HW, nnb) : 0;
     const int lds_tiles = gather && lds_lists > g.tile_bytes ? lds_lists : g.tile_bytes;
     if ((e = allow_dynamic_lds<wide_code_tiles_kernel>(lds_tiles)) != hipSuccess) return e;
     p.zero[0] = a.d_code; p.zero[1] = a.d_code_pos;
@@ -792,11 +834,12 @@ hipError_t launch_wide_bwd(const WideBwdArgs& a, hipStream_t stream)
     const int zero_blocks = 2 * (int)((p.zero_floats + WB_ZERO_CHUNK - 1) / WB_ZERO_CHUNK);
     const int lds = 128 * WB_GS * 4 + 2 * g.tile_bytes;
     if ((e = allow_dynamic_lds<wide_bwd_kernel>(lds)) != hipSuccess) return e;
-    for (int win = 0; win < g.nwin; ++win) {
+    const WideWindows windows = wide_windows(K);
+    for (int win = 0; win < windows.nwin; ++win) {
         // one pass per window of code channels (K <= 88: one): its tiles, then both GEMMs into the window's columns of the row gradients.  The
         // lists / the zeroing ride with the first pass
-        p.k0 = win * g.Kc;
-        p.Kc = K - p.k0 < g.Kc ? K - p.k0 : g.Kc;
+        p.k0 = windows.k0(win);
+        p.Kc = windows.kc(win, K);
         const int extra = win == 0 ? list_blocks + zero_blocks : 0;
         hipLaunchKernelGGL(wide_code_tiles_kernel, dim3(g.n_img * g.nb + extra), dim3(512), lds_tiles, stream, p, q, win == 0 ? list_blocks : 0);
         hipLaunchKernelGGL(wide_bwd_kernel, dim3(g.n_img), dim3(WB_THREADS), lds, stream, p);

@@ -14,6 +14,7 @@
 //                       products, fp32 accumulate), the tile is stored straight from the accumulators (each wave
 //                       instruction writes 128-byte row segments).  Output-write bound at C = 384.
 #include "corr_common.h"
+#include "corr_wide_plan.h"
 #include "host_util.h"
 #include "launchers.h"
 
@@ -231,10 +232,10 @@ __global__ void __launch_bounds__(NTHREADS) dense_tile_kernel(const DenseParams 
 // the accumulators while the next block's copies fly.  Workgroups of image n sit on XCD n % 8 (they stream the same B image).  The prep
 // kernel runs for the B side only.
 constexpr int DR_NST = 3;
-constexpr int DR_MAXCH = 6;
 constexpr int DR_PKS = 68;        // floats per row of a wave's parked 32 x 64 half slab (272 B: conflict-free 16-byte reads along a row)
 static_assert(4 * 32 * DR_PKS * 4 <= DC_SIDE, "the parked half slabs of four waves fit one ring slot");
 static_assert(DC_SIDE % 4096 == 0, "whole 1 KB pieces per wave");
+static_assert(PANEL_KC == KC, "corr_wide_plan.h counts the chunks of an operand image");
 __device__ __forceinline__ void dense_dma_piece(const unsigned char* gsrc_lane, unsigned lds_addr)
 {
     unsigned keep;
@@ -755,34 +756,37 @@ hipError_t launch_dense_corr_panels(const void* imgA, const float* rsA, int imag
 hipError_t launch_dense_corr_panels_seg(const void* imgA, const float* rsA, int imagesA, const void* imgB, const float* rsB, int B, int C, int M, int N,
                                         float* out, float* out1, float* out2, int seg, float* rowsum, hipStream_t stream)
 {
+    // row pair / row block / tile (+ a row-sum launch): corr_wide_plan.h
+    const PanelGemmPlan plan = panel_gemm_plan(C, M, N, seg > 0, rowsum != nullptr, knob(KNOB_DEBUG));
     DenseParams prm{};
     prm.out = out;
     prm.B = B; prm.C = C; prm.M = M; prm.N = N; prm.W1 = 1; prm.W2 = 1;
-    prm.nbA = (M + TP - 1) / TP; prm.nbB = (N + TP - 1) / TP; prm.NCH = (C + KC - 1) / KC;
+    prm.nbA = plan.nbA; prm.nbB = plan.nbB; prm.NCH = plan.NCH;
     prm.imgA = const_cast<void*>(imgA); prm.imgB = const_cast<void*>(imgB);
     prm.rsA = const_cast<float*>(rsA); prm.rsB = const_cast<float*>(rsB);
     prm.a_mod = imagesA;
     prm.rowsum = rowsum;
     prm.out1 = out1; prm.out2 = out2; prm.seg = seg;
     prm.normalize = (knob(KNOB_DEBUG) >> 16) & 7;          // (tools: ablations of the row-block kernel)
-    if (prm.NCH <= DR_MAXCH && !(knob(KNOB_DEBUG) & 8192)) {
-        if (prm.nbA >= 2 && prm.NCH <= 2 && !(knob(KNOB_DEBUG) & (1 << 20))) {  // (debug bit 20: one row block per workgroup)
-            const int ldsp = 2 * DC_SIDE + 1024 + (DR2_THREADS / 64) * 32 * DR_PKS * 4;
-            return launch<dense_rowpair_kernel<2>>(dim3((unsigned)(((B + 7) / 8) * 8 * ((prm.nbA + 1) / 2))), dim3(DR2_THREADS), ldsp, stream, prm);
-        }
-        const dim3 grid((unsigned)(((B + 7) / 8) * 8 * prm.nbA));
-        if (knob(KNOB_DEBUG) & (1 << 19)) {                     // (tools: four ring stages - three copies in flight -, one workgroup per CU)
-            const int lds3 = 4 * DC_SIDE + 512;
-            return launch<dense_rowblock_kernel<true, 4>>(grid, dim3(NTHREADS), lds3, stream, prm);
-        }
-        const int lds2 = 2 * DC_SIDE + 512;
-        return launch<dense_rowblock_kernel<true, 2>>(grid, dim3(NTHREADS), lds2, stream, prm);
+    const dim3 grid((unsigned)(((B + 7) / 8) * 8 * prm.nbA));
+    switch (plan.kernel) {
+    case PanelGemm::RowPair: {
+        const int ldsp = 2 * DC_SIDE + 1024 + (DR2_THREADS / 64) * 32 * DR_PKS * 4;
+        return launch<dense_rowpair_kernel<DR2_MAXCH>>(dim3((unsigned)(((B + 7) / 8) * 8 * ((prm.nbA + 1) / 2))), dim3(DR2_THREADS), ldsp, stream, prm);
     }
-    if (seg > 0) return hipErrorInvalidValue;                 // (segmented outputs: the row-block kernel only - codes, K <= 384)
-    const int lds = 2 * DC_SIDE;
-    hipError_t e = launch<dense_tile_kernel>(dim3(prm.nbB, prm.nbA, B), dim3(NTHREADS), lds, stream, prm);
-    if (e == hipSuccess && rowsum) e = launch_rowsum(out, rowsum, (long long)B * M, N, stream);        // (the tile kernel's workgroups see 128 columns)
-    return e;
+    case PanelGemm::RowBlock4:                                 // (tools: four ring stages - three copies in flight -, one workgroup per CU)
+        return launch<dense_rowblock_kernel<true, 4>>(grid, dim3(NTHREADS), 4 * DC_SIDE + 512, stream, prm);
+    case PanelGemm::RowBlock:
+        return launch<dense_rowblock_kernel<true, 2>>(grid, dim3(NTHREADS), 2 * DC_SIDE + 512, stream, prm);
+    case PanelGemm::Tile: {
+        hipError_t e = launch<dense_tile_kernel>(dim3(prm.nbB, prm.nbA, B), dim3(NTHREADS), 2 * DC_SIDE, stream, prm);
+        if (e == hipSuccess && plan.rowsum_launch) e = launch_rowsum(out, rowsum, (long long)B * M, N, stream);        // (the tile kernel's workgroups see 128 columns)
+        return e;
+    }
+    case PanelGemm::Invalid:
+        break;
+    }
+    return hipErrorInvalidValue;                              // (segmented outputs: the row kernels only - codes, K <= 384)
 }
 
 size_t dense_panel_image_bytes(int C, int P)

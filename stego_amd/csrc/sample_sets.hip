@@ -12,6 +12,7 @@
 // (n, point): 16-byte loads along the channels of a channels-last map, scalar loads for any other layout.  Used by
 // stego_amd.modules.ContrastiveCorrelationLoss.generic_forward (cfg.feature_samples > 11, cfg.dim > 128).
 #include "corr_common.h"
+#include "corr_wide_plan.h"
 #include "host_util.h"
 #include "launchers.h"
 #include "../../include/stego_corr.h"
@@ -295,14 +296,12 @@ static GatherParams make_params(const StegoMap* map, const int64_t* index, int32
     return p;
 }
 
-static int panel_vw(const StegoMap* map, int C, const float* rows_out)
+static MapFacts map_facts(const StegoMap* map)
 {
-    auto aligned = [&](int vw) {
-        return map->stride_c == 1 && C % vw == 0 && C <= 256 * vw && map->stride_n % vw == 0 && map->stride_h % vw == 0 && map->stride_w % vw == 0 &&
-               reinterpret_cast<uintptr_t>(map->data) % (4 * vw) == 0 && (!rows_out || reinterpret_cast<uintptr_t>(rows_out) % (4 * vw) == 0);
-    };
-    return aligned(4) ? 4 : aligned(2) ? 2 : 0;
+    return MapFacts{map->stride_n, map->stride_c, map->stride_h, map->stride_w, reinterpret_cast<uintptr_t>(map->data)};
 }
+
+static_assert(PANEL_KC == KC && PANEL_MAXJ == RowSampler<4>::MAXJ && PANEL_MAXJ == RowSampler<2>::MAXJ, "corr_wide_plan.h states the sampler's limits");
 
 static PanelSide panel_side(const StegoMap* map, int C, void* panels, float* row_scale, float* rows_out, float* inv_out)
 {
@@ -329,7 +328,8 @@ hipError_t launch_sample_panels2(const StegoMap* map, int C, void* panels, float
     pp.side[1] = map2 ? panel_side(map2, C2, panels2, row_scale2, rows_out2, inv_out2) : pp.side[0];
     pp.nb = (pp.g.P + TP - 1) / TP;
     pp.normalize = (normalize ? 1 : 0) | ((knob(KNOB_DEBUG_SAMPLE) & (1 << 16)) ? 2 : 0);
-    const int v1 = panel_vw(map, C, rows_out), v2 = map2 ? panel_vw(map2, C2, rows_out2) : -1;
+    const int v1 = panel_vw(map_facts(map), C, reinterpret_cast<uintptr_t>(rows_out));
+    const int v2 = map2 ? panel_vw(map_facts(map2), C2, reinterpret_cast<uintptr_t>(rows_out2)) : -1;
     const dim3 grid((unsigned)(((long long)N * pp.g.P + 3) / 4)), block(256);
     // vector widths of the two sides (panel_vw: 4, 2 or 0; -1: no second map)
     return with_const<4, 2, 0>(v1, [&](auto V1) {
@@ -375,8 +375,7 @@ int stego_sample(const StegoMap* map, const int64_t* index, int32_t N, int32_t C
     if (rc != STEGO_OK) return rc;
     if (N == 0) return STEGO_OK;
     const GatherParams p = make_params(map, index, N, C, H, W, coords, n_coords, S, out, nullptr);
-    const bool vec = map->stride_c == 1 && C % 4 == 0 && map->stride_n % 4 == 0 && map->stride_h % 4 == 0 && map->stride_w % 4 == 0 &&
-                     reinterpret_cast<uintptr_t>(map->data) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
+    const bool vec = sample_gather_vec(map_facts(map), C, reinterpret_cast<uintptr_t>(out));
     const dim3 grid((unsigned)(((long long)N * p.P + 3) / 4)), block(256);
     if (vec) hipLaunchKernelGGL(sample_gather_kernel<true>, grid, block, 0, static_cast<hipStream_t>(stream), p);
     else hipLaunchKernelGGL(sample_gather_kernel<false>, grid, block, 0, static_cast<hipStream_t>(stream), p);
