@@ -206,6 +206,16 @@ SALIENCE_ERR_SIZE, SALIENCE_ERR_SAMPLES, SALIENCE_ERR_DTYPE = 130, 131, 132
 SALIENCE_U8, SALIENCE_F32 = 0, 1
 SALIENCE_MAX_PIXELS, SALIENCE_MAX_S, SALIENCE_MAX_B = 1 << 20, 16, 65535
 
+
+class StegoRecDesc(Structure):
+    """include/stego_rec.h"""
+    _fields_ = [(n, c_int32) for n in ("B", "K", "C", "h", "w")]
+
+
+REC_ERR_DIM, REC_ERR_SIZE = 140, 141
+REC_MAX_K, REC_MAX_C, REC_MAX_B, REC_MAX_SIDE, REC_MAX_TOKENS = 128, 1024, 65535, 2048, 1 << 24
+REC_TILE, REC_MAX_WORKGROUPS, REC_LAUNCHES = 32, 64, 2
+
 _H = POINTER(StegoHeadDesc)
 _D = POINTER(StegoCorrDesc)
 _M = POINTER(StegoMap)
@@ -256,6 +266,9 @@ SIGNATURES = {
     "stego_aug_align_workspace_bytes": (c_size_t, [POINTER(StegoAugAlignDesc)]),
     "stego_aug_align_plan": (c_int32, [POINTER(StegoAugAlignDesc), POINTER(c_size_t), POINTER(c_int64)]),
     "stego_aug_align": (c_int32, [POINTER(StegoAugAlignDesc), _M, _M, _P, _P, _M, _M, _P, c_size_t, _P]),
+    "stego_rec_loss_workspace_bytes": (c_size_t, [POINTER(StegoRecDesc)]),
+    "stego_rec_loss_plan": (c_int32, [POINTER(StegoRecDesc), POINTER(c_size_t), POINTER(c_int64)]),
+    "stego_rec_loss": (c_int32, [POINTER(StegoRecDesc), _M, _M, _P, _P, _P, _M, _P, _P, _P, c_size_t, _P]),
     "stego_abi_version": (c_int32, []),
     "stego_debug_set": (c_int32, [c_int32, c_int32]),
     "stego_debug_occupy": (c_int32, [c_int32, c_int32, c_int32, _P]),
@@ -1867,3 +1880,56 @@ def aug_align(code, code_aug, coord, need_code=True, need_code_aug=True):
         _check(aug_align_raw(desc, _map(code), _map(code_aug), coord, loss, _map(d_code) if need_code else None,
                              _map(d_code_aug) if need_code_aug else None, ws, n, _stream()))
     return loss, d_code, d_code_aug
+
+
+# ---- fused reconstruction loss, forward and backward (include/stego_rec.h; stego_amd.rec_loss wraps it for the trainer)
+def rec_desc(B, K, C, h, w):
+    return StegoRecDesc(int(B), int(K), int(C), int(h), int(w))
+
+
+def rec_loss_workspace_bytes(desc):
+    return int(load().stego_rec_loss_workspace_bytes(byref(desc)))
+
+
+def rec_loss_plan(desc):
+    """stego_rec_loss_plan (host only) -> (return code, [(LDS bytes, workgroups) of the tiles and the finish launch])."""
+    lds, wgs = (c_size_t * REC_LAUNCHES)(), (c_int64 * REC_LAUNCHES)()
+    rc = load().stego_rec_loss_plan(byref(desc), lds, wgs)
+    return int(rc), [(int(a), int(b)) for a, b in zip(lds, wgs)]
+
+
+def rec_loss_raw(desc, code, feats, weight, bias, loss, d_code, d_weight, d_bias, workspace, workspace_bytes, stream=None):
+    """stego_rec_loss with every argument given: `code`, `feats` and `d_code` are StegoMap (or None), the rest raw addresses or
+    tensors (tests: the error codes) -> the return code, unchecked."""
+    return int(load().stego_rec_loss(byref(desc) if desc is not None else None, _ref(code), _ref(feats), _addr(weight), _addr(bias),
+                                     _addr(loss), _ref(d_code), _addr(d_weight), _addr(d_bias), _addr(workspace), int(workspace_bytes),
+                                     stream if stream is not None else None))
+
+
+def rec_loss(code, feats, weight, bias, need_code=True, need_weight=True, need_bias=True):
+    """stego_rec_loss: code float32 [B, K, h, w] and feats float32 [B, C, h, w] (any strides), weight [C, K] (or the convolution's
+    [C, K, 1, 1]) and bias [C], all on one HIP device -> (loss float32 [1], d_code, d_weight, d_bias; None where not asked for), the
+    gradients for a unit upstream, d_code in the layout of `code`, d_weight in the shape of `weight`.  The workspace comes from torch's
+    caching allocator, as for the other fused calls."""
+    _require_dev(code, feats, weight, bias)
+    if code.dim() != 4 or feats.dim() != 4 or feats.shape[0] != code.shape[0] or feats.shape[2:] != code.shape[2:]:
+        raise ValueError("rec_loss expects a code [B, K, h, w] and feats [B, C, h, w], got %s and %s" % (tuple(code.shape), tuple(feats.shape)))
+    B, K, h, w = code.shape
+    C = feats.shape[1]
+    if weight.numel() != C * K or weight.shape[:2] != (C, K) or tuple(bias.shape) != (C,):
+        raise ValueError("rec_loss expects a weight [%d, %d] and a bias [%d], got %s and %s" % (C, K, C, tuple(weight.shape), tuple(bias.shape)))
+    weight, bias = _dense(weight, torch.float32), _dense(bias, torch.float32)
+    dev = code.device
+    desc = rec_desc(B, K, C, h, w)
+    n = rec_loss_workspace_bytes(desc)
+    if n == 0:
+        _check(rec_loss_raw(desc, _map(code), _map(feats), weight, bias, 16, None, None, None, 16, 0))       # raises with the descriptor's code
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    d_code = torch.empty_like(code) if need_code else None
+    d_weight = torch.empty_like(weight) if need_weight else None
+    d_bias = torch.empty_like(bias) if need_bias else None
+    ws = _empty_bytes(n, dev)
+    with _on_device(dev):
+        _check(rec_loss_raw(desc, _map(code), _map(feats), weight, bias, loss, _map(d_code) if need_code else None, d_weight, d_bias,
+                            ws, n, _stream()))
+    return loss, d_code, d_weight, d_bias

@@ -19,6 +19,7 @@
 #include "../../include/stego_optim.h"
 #include "../../include/stego_stitch.h"
 #include "../../include/stego_salience.h"
+#include "../../include/stego_rec.h"
 #include "corr_wide.h"
 #include "launchers.h"
 
@@ -373,6 +374,8 @@ const char* stego_error_string(int code)
         case STEGO_ERR_SALIENCE_SIZE: return "salience draws: B outside [1, 65535], H or W < 1, or H * W > 2^20 (include/stego_salience.h)";
         case STEGO_ERR_SALIENCE_SAMPLES: return "salience draws: S outside [1, 16]";
         case STEGO_ERR_SALIENCE_DTYPE: return "salience draws: mask_dtype is neither STEGO_SALIENCE_U8 nor STEGO_SALIENCE_F32";
+        case STEGO_ERR_REC_DIM: return "rec loss: K outside [1, 128] or C outside [1, 1024] (include/stego_rec.h)";
+        case STEGO_ERR_REC_SIZE: return "rec loss: B outside [1, 65535], h or w outside [1, 2048], or B * h * w > 2^24";
         case STEGO_ERR_CRF_RANGE: return "dense CRF: a lattice coordinate would leave the packed key (image too large for its standard deviations)";
         default: return code >= STEGO_ERR_HIP ? "HIP runtime error (code - 1000 = hipError_t)" : "unknown error";
     }

@@ -26,6 +26,7 @@ from .augment import Augmenter, aug_alignment_loss, needs_torchvision
 from .featurizers import ClusterLookup, ContrastiveCRFLoss, DinoFeaturizer, FeaturePyramidNet
 from .modules import ContrastiveCorrelationLoss, norm, sample
 from .probe_train import probe_losses, torch_probe_losses
+from .rec_loss import rec_loss as native_rec_loss
 from .metrics import DeviceUnsupervisedMetrics, probe_confusion
 from .utils import UnsupervisedMetrics, one_hot_feats, prep_args, resize
 
@@ -286,7 +287,11 @@ class LitUnsupervisedSegmenter(nn.Module):
             loss += corr_total * cfg.correspondence_weight
 
         if cfg.rec_weight > 0:
-            rec_loss = -(norm(self.decoder(code)) * norm(feats)).sum(1).mean()
+            if getattr(cfg, "native_rec_loss", False):
+                # the same number from one fused call that writes no reconstructed map (include/stego_rec.h)
+                rec_loss = native_rec_loss(code, feats, self.decoder)
+            else:
+                rec_loss = -(norm(self.decoder(code)) * norm(feats)).sum(1).mean()
             self.log('loss/rec', rec_loss, **log_args)
             loss += cfg.rec_weight * rec_loss
 
