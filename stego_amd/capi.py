@@ -31,8 +31,6 @@ class StegoCorrDesc(Structure):
                 ("neg_inter_shift", c_float), ("precision", c_int32), ("flags", c_int32)]
 
 
-# name -> (restype, argtypes); every symbol include/stego_corr.h declares
-_P = c_void_p
 class StegoVitDesc(Structure):
     """include/stego_vit.h"""
     _fields_ = [(n, c_int32) for n in ("B", "H", "W", "patch", "D", "depth", "heads", "hidden", "precision")]
@@ -216,6 +214,8 @@ REC_ERR_DIM, REC_ERR_SIZE = 140, 141
 REC_MAX_K, REC_MAX_C, REC_MAX_B, REC_MAX_SIDE, REC_MAX_TOKENS = 128, 1024, 65535, 2048, 1 << 24
 REC_TILE, REC_MAX_WORKGROUPS, REC_LAUNCHES = 32, 64, 2
 
+# name -> (restype, argtypes); every symbol include/stego_corr.h declares
+_P = c_void_p
 _H = POINTER(StegoHeadDesc)
 _D = POINTER(StegoCorrDesc)
 _M = POINTER(StegoMap)
@@ -393,6 +393,26 @@ def _map(t):
 
 def _ptr(t):
     return None if t is None else t.data_ptr()
+
+
+def _addr(x):
+    """A tensor's address; a raw address or None as it is (the *_raw wrappers: tests hand them NULL and misaligned pointers)."""
+    return _ptr(x) if torch.is_tensor(x) else x
+
+
+def _ref(m):
+    """byref of a StegoMap, or NULL."""
+    return byref(m) if m is not None else None
+
+
+_desc_ref = _ref        # ... of a descriptor or a window layout, or NULL
+
+
+def _launch_plan(fn, desc, n):
+    """An array-style stego_*_plan export (host only) -> (return code, [(LDS bytes, workgroups) of each of the n launches])."""
+    lds, wgs = (c_size_t * n)(), (c_int64 * n)()
+    rc = fn(byref(desc), lds, wgs)
+    return int(rc), [(int(a), int(b)) for a, b in zip(lds, wgs)]
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -1228,11 +1248,29 @@ def probe_head_plan(desc):
 def probe_head_raw(desc, code, code_flip, lin_w, lin_b, centroids, lin_out, clu_out, stream=None):
     """stego_probe_head with every argument given: `code` / `code_flip` are StegoMap (or None), the rest raw addresses or tensors
     (tests: the error codes) -> the return code, unchecked."""
-    def addr(x):
-        return _ptr(x) if torch.is_tensor(x) else x
-    return int(load().stego_probe_head(byref(desc), byref(code) if code is not None else None,
-                                       byref(code_flip) if code_flip is not None else None, addr(lin_w), addr(lin_b), addr(centroids),
-                                       addr(lin_out), addr(clu_out), stream if stream is not None else None))
+    return int(load().stego_probe_head(byref(desc), _ref(code),
+                                       _ref(code_flip), _addr(lin_w), _addr(lin_b), _addr(centroids),
+                                       _addr(lin_out), _addr(clu_out), stream if stream is not None else None))
+
+
+def _probe_weights(lin_w, lin_b, centroids, n_lin, n_clu, K):
+    """The probes' weights as dense float32 tensors, None for a skipped probe (n == 0); their shapes checked against K."""
+    def weights(t, n):
+        return _dense(t, torch.float32) if t is not None and n else None
+    lw, lb, ce = weights(lin_w, n_lin), weights(lin_b, n_lin), weights(centroids, n_clu)
+    if lw is not None and tuple(lw.shape) != (n_lin, K) or ce is not None and tuple(ce.shape) != (n_clu, K):
+        raise ValueError("probe weights %s / %s do not match K = %d" % (None if lw is None else tuple(lw.shape),
+                                                                        None if ce is None else tuple(ce.shape), K))
+    return lw, lb, ce
+
+
+def _probe_out(kind, n, lead, H, W, dev):
+    """A probe's output: None when skipped, int64 [*lead, H, W] for "argmax", else float32 [*lead, n, H, W]."""
+    if kind == PROBE_SKIP:
+        return None
+    if kind == PROBE_ARGMAX:
+        return torch.empty(*lead, H, W, dtype=torch.int64, device=dev)
+    return torch.empty(*lead, n, H, W, dtype=torch.float32, device=dev)
 
 
 def probe_head(code, code_flip, lin_w, lin_b, centroids, size, lin_kind, clu_kind, alpha):
@@ -1248,21 +1286,8 @@ def probe_head(code, code_flip, lin_w, lin_b, centroids, size, lin_kind, clu_kin
     if code_flip is not None and tuple(code_flip.shape) != tuple(code.shape):
         raise ValueError("code_flip %s does not match code %s" % (tuple(code_flip.shape), tuple(code.shape)))
     dev = code.device
-
-    def out(kind, n):
-        if kind == PROBE_SKIP:
-            return None
-        if kind == PROBE_ARGMAX:
-            return torch.empty(B, H, W, dtype=torch.int64, device=dev)
-        return torch.empty(B, n, H, W, dtype=torch.float32, device=dev)
-
-    def weights(t, n):
-        return _dense(t, torch.float32) if t is not None and n else None
-    lw, lb, ce = weights(lin_w, n_lin), weights(lin_b, n_lin), weights(centroids, n_clu)
-    if lw is not None and tuple(lw.shape) != (n_lin, K) or ce is not None and tuple(ce.shape) != (n_clu, K):
-        raise ValueError("probe weights %s / %s do not match K = %d" % (None if lw is None else tuple(lw.shape),
-                                                                        None if ce is None else tuple(ce.shape), K))
-    lo, co = out(lk, n_lin), out(ck, n_clu)
+    lw, lb, ce = _probe_weights(lin_w, lin_b, centroids, n_lin, n_clu, K)
+    lo, co = _probe_out(lk, n_lin, (B,), H, W, dev), _probe_out(ck, n_clu, (B,), H, W, dev)
     desc = probe_desc(B, K, h, w, H, W, n_lin, n_clu, lk, ck, alpha)
     with _on_device(dev):
         _check(probe_head_raw(desc, _map(code), _map(code_flip) if code_flip is not None else None, lw, lb, ce, lo, co, _stream()))
@@ -1289,11 +1314,9 @@ def stitch_probe_plan(desc):
 def stitch_probe_raw(desc, code, code_flip, lin_w, lin_b, centroids, lin_out, clu_out, stream=None):
     """stego_stitch_probe with every argument given: `code` / `code_flip` are StegoMap (or None), the rest raw addresses or tensors
     (tests: the error codes) -> the return code, unchecked."""
-    def addr(x):
-        return _ptr(x) if torch.is_tensor(x) else x
-    return int(load().stego_stitch_probe(byref(desc) if desc is not None else None, byref(code) if code is not None else None,
-                                         byref(code_flip) if code_flip is not None else None, addr(lin_w), addr(lin_b), addr(centroids),
-                                         addr(lin_out), addr(clu_out), stream if stream is not None else None))
+    return int(load().stego_stitch_probe(_desc_ref(desc), _ref(code),
+                                         _ref(code_flip), _addr(lin_w), _addr(lin_b), _addr(centroids),
+                                         _addr(lin_out), _addr(clu_out), stream if stream is not None else None))
 
 
 def stitch_probe(code, code_flip, lin_w, lin_b, centroids, size, win, stride, lin_kind, clu_kind, alpha):
@@ -1310,24 +1333,11 @@ def stitch_probe(code, code_flip, lin_w, lin_b, centroids, size, win, stride, li
     if code_flip is not None and tuple(code_flip.shape) != tuple(code.shape):
         raise ValueError("code_flip %s does not match code %s" % (tuple(code_flip.shape), tuple(code.shape)))
     dev = code.device
-
-    def out(kind, n):
-        if kind == PROBE_SKIP:
-            return None
-        if kind == PROBE_ARGMAX:
-            return torch.empty(H, W, dtype=torch.int64, device=dev)
-        return torch.empty(n, H, W, dtype=torch.float32, device=dev)
-
-    def weights(t, n):
-        return _dense(t, torch.float32) if t is not None and n else None
-    lw, lb, ce = weights(lin_w, n_lin), weights(lin_b, n_lin), weights(centroids, n_clu)
-    if lw is not None and tuple(lw.shape) != (n_lin, K) or ce is not None and tuple(ce.shape) != (n_clu, K):
-        raise ValueError("probe weights %s / %s do not match K = %d" % (None if lw is None else tuple(lw.shape),
-                                                                        None if ce is None else tuple(ce.shape), K))
+    lw, lb, ce = _probe_weights(lin_w, lin_b, centroids, n_lin, n_clu, K)
     desc = stitch_desc(H, W, win, stride, T, K, hc, wc, n_lin, n_clu, lk, ck, alpha)
     if stitch_probe_plan(desc)[0] == 0:     # an invalid descriptor: name the error before any output is sized from it
         _check(stitch_probe_raw(desc, None, None, None, None, None, None, None))
-    lo, co = out(lk, n_lin), out(ck, n_clu)
+    lo, co = _probe_out(lk, n_lin, (), H, W, dev), _probe_out(ck, n_clu, (), H, W, dev)
     with _on_device(dev):
         _check(stitch_probe_raw(desc, _map(code), _map(code_flip) if code_flip is not None else None, lw, lb, ce, lo, co, _stream()))
     return lo, co
@@ -1336,10 +1346,8 @@ def stitch_probe(code, code_flip, lin_w, lin_b, centroids, size, win, stride, li
 def window_gather_raw(layout, img, t0, n, out, out_flip, stream=None):
     """stego_window_gather with every argument given: `img` is a StegoMap (or None), `out` / `out_flip` raw addresses or tensors ->
     the return code, unchecked."""
-    def addr(x):
-        return _ptr(x) if torch.is_tensor(x) else x
-    return int(load().stego_window_gather(byref(layout) if layout is not None else None, byref(img) if img is not None else None,
-                                          int(t0), int(n), addr(out), addr(out_flip), stream if stream is not None else None))
+    return int(load().stego_window_gather(_desc_ref(layout), _ref(img),
+                                          int(t0), int(n), _addr(out), _addr(out_flip), stream if stream is not None else None))
 
 
 def window_gather(img, win, stride, t0, n, flip=False):
@@ -1378,15 +1386,11 @@ def probe_confusion_plan(desc):
     return int(n), ty.value, tx.value
 
 
-def _addr(x):
-    return _ptr(x) if torch.is_tensor(x) else x
-
-
 def probe_confusion_raw(desc, code, code_flip, lin_w, lin_b, centroids, labels, lin_counts, clu_counts, stream=None):
     """stego_probe_confusion with every argument given: `code` / `code_flip` are StegoMap (or None), the rest raw addresses or
     tensors (tests: the error codes) -> the return code, unchecked."""
-    return int(load().stego_probe_confusion(byref(desc) if desc is not None else None, byref(code) if code is not None else None,
-                                            byref(code_flip) if code_flip is not None else None, _addr(lin_w), _addr(lin_b),
+    return int(load().stego_probe_confusion(_desc_ref(desc), _ref(code),
+                                            _ref(code_flip), _addr(lin_w), _addr(lin_b),
                                             _addr(centroids), _addr(labels), _addr(lin_counts), _addr(clu_counts),
                                             stream if stream is not None else None))
 
@@ -1436,7 +1440,7 @@ def probe_confusion(code, code_flip, lin_w, lin_b, centroids, labels, lin_counts
 
 def confusion_raw(desc, pred, labels, counts, stream=None):
     """stego_confusion with raw addresses or tensors (tests: the error codes) -> the return code, unchecked."""
-    return int(load().stego_confusion(byref(desc) if desc is not None else None, _addr(pred), _addr(labels), _addr(counts),
+    return int(load().stego_confusion(_desc_ref(desc), _addr(pred), _addr(labels), _addr(counts),
                                       stream if stream is not None else None))
 
 
@@ -1486,7 +1490,7 @@ def adam_desc(n_segments, groups, zero_grads, grad_elems, state_elems, n_groups=
 def adam_plan(desc, segments_host):
     """stego_adam_plan (host only) -> (return code, grid, chunk, n_chunks); the last three are 0 when the code is not 0."""
     grid, chunk, n = c_int32(0), c_int32(0), c_int64(0)
-    rc = load().stego_adam_plan(byref(desc) if desc is not None else None,
+    rc = load().stego_adam_plan(_desc_ref(desc),
                                 ctypes.addressof(segments_host) if segments_host is not None else None, byref(grid), byref(chunk),
                                 byref(n))
     return int(rc), grid.value, chunk.value, n.value
@@ -1495,7 +1499,7 @@ def adam_plan(desc, segments_host):
 def adam_step_raw(desc, segments_host, segments, grads, exp_avg, exp_avg_sq, steps, ticket, stream=None):
     """stego_adam_step with every argument given: `segments_host` a ctypes array (or None), the rest raw addresses or tensors (tests:
     the error codes) -> the return code, unchecked."""
-    return int(load().stego_adam_step(byref(desc) if desc is not None else None,
+    return int(load().stego_adam_step(_desc_ref(desc),
                                       ctypes.addressof(segments_host) if segments_host is not None else None, _addr(segments),
                                       _addr(grads), _addr(exp_avg), _addr(exp_avg_sq), _addr(steps), _addr(ticket),
                                       stream if stream is not None else None))
@@ -1530,11 +1534,9 @@ def probe_train_raw(desc, code, label, lin_w, lin_b, clusters, losses, n_valid, 
                     stream=None):
     """stego_probe_train with every argument given: `code` is a StegoMap (or None), the rest raw addresses or tensors (tests: the error
     codes) -> the return code, unchecked."""
-    def addr(x):
-        return _ptr(x) if torch.is_tensor(x) else x
-    return int(load().stego_probe_train(byref(desc), byref(code) if code is not None else None, addr(label), addr(lin_w), addr(lin_b),
-                                        addr(clusters), addr(losses), addr(n_valid), addr(d_lin_w), addr(d_lin_b), addr(d_clusters),
-                                        addr(workspace), int(workspace_bytes), stream if stream is not None else None))
+    return int(load().stego_probe_train(byref(desc), _ref(code), _addr(label), _addr(lin_w), _addr(lin_b),
+                                        _addr(clusters), _addr(losses), _addr(n_valid), _addr(d_lin_w), _addr(d_lin_b), _addr(d_clusters),
+                                        _addr(workspace), int(workspace_bytes), stream if stream is not None else None))
 
 
 def probe_train(code, label, lin_w, lin_b, clusters):
@@ -1592,10 +1594,8 @@ def pr_plan(desc):
 def pr_accumulate_raw(desc, a, b, labels_a, labels_b, index_b, coords1, coords2, hist, stream=None):
     """stego_pr_accumulate with every argument given: `a` / `b` are StegoMap (or None), the rest raw addresses or tensors (tests: the
     error codes) -> the return code, unchecked."""
-    def addr(x):
-        return _ptr(x) if torch.is_tensor(x) else x
-    return int(load().stego_pr_accumulate(byref(desc), byref(a) if a is not None else None, byref(b) if b is not None else None,
-                                          addr(labels_a), addr(labels_b), addr(index_b), addr(coords1), addr(coords2), addr(hist),
+    return int(load().stego_pr_accumulate(byref(desc), _ref(a), _ref(b),
+                                          _addr(labels_a), _addr(labels_b), _addr(index_b), _addr(coords1), _addr(coords2), _addr(hist),
                                           stream if stream is not None else None))
 
 
@@ -1658,10 +1658,8 @@ def heat_workspace_views(desc, ws):
 def corr_heatmaps_raw(desc, src, tgt, index_t, points, heat, peak, best, workspace, workspace_bytes, stream=None):
     """stego_corr_heatmaps with every argument given: `src` / `tgt` are StegoMap (or None), the rest raw addresses or tensors (tests:
     the error codes) -> the return code, unchecked."""
-    def addr(x):
-        return _ptr(x) if torch.is_tensor(x) else x
-    return int(load().stego_corr_heatmaps(byref(desc), byref(src) if src is not None else None, byref(tgt) if tgt is not None else None,
-                                          addr(index_t), addr(points), addr(heat), addr(peak), addr(best), addr(workspace),
+    return int(load().stego_corr_heatmaps(byref(desc), _ref(src), _ref(tgt),
+                                          _addr(index_t), _addr(points), _addr(heat), _addr(peak), _addr(best), _addr(workspace),
                                           int(workspace_bytes), stream if stream is not None else None))
 
 
@@ -1712,21 +1710,14 @@ def crf_loss_workspace_bytes(desc):
 
 def crf_loss_plan(desc):
     """stego_crf_loss_plan (host only) -> (return code, [(LDS bytes, workgroups) of the prepare, pairs and finish launch])."""
-    lds, wgs = (c_size_t * CRFLOSS_LAUNCHES)(), (c_int64 * CRFLOSS_LAUNCHES)()
-    rc = load().stego_crf_loss_plan(byref(desc), lds, wgs)
-    return int(rc), [(int(a), int(b)) for a, b in zip(lds, wgs)]
+    return _launch_plan(load().stego_crf_loss_plan, desc, CRFLOSS_LAUNCHES)
 
 
 def crf_loss_raw(desc, guidance, code, coords, loss, per_image, d_code, workspace, workspace_bytes, stream=None):
     """stego_crf_loss with every argument given: `guidance`, `code` and `d_code` are StegoMap (or None), the rest raw addresses or
     tensors (tests: the error codes) -> the return code, unchecked."""
-    def addr(x):
-        return _ptr(x) if torch.is_tensor(x) else x
-
-    def ref(m):
-        return byref(m) if m is not None else None
-    return int(load().stego_crf_loss(byref(desc) if desc is not None else None, ref(guidance), ref(code), addr(coords), addr(loss),
-                                     addr(per_image), ref(d_code), addr(workspace), int(workspace_bytes),
+    return int(load().stego_crf_loss(_desc_ref(desc), _ref(guidance), _ref(code), _addr(coords), _addr(loss),
+                                     _addr(per_image), _ref(d_code), _addr(workspace), int(workspace_bytes),
                                      stream if stream is not None else None))
 
 
@@ -1761,14 +1752,6 @@ def crf_loss(guidance, code, coords, size, params, normalize=True, need_grad=Tru
 
 
 # ---- device-side augmented views and the fused aug-alignment loss (include/stego_aug.h; stego_amd.augment wraps them for the trainer)
-def _addr(x):
-    return _ptr(x) if torch.is_tensor(x) else x
-
-
-def _ref(m):
-    return byref(m) if m is not None else None
-
-
 def aug_desc(B, H, W, R):
     return StegoAugDesc(int(B), int(H), int(W), int(R))
 
@@ -1777,7 +1760,7 @@ def aug_check_params(desc, records):
     """stego_augment_check_params (host only): `records` a ctypes array of StegoAugParams (or None) ->
     (return code, index of the first bad record or -1, whether a record applies contrast)."""
     bad, contrast = c_int64(-1), c_int32(0)
-    rc = load().stego_augment_check_params(byref(desc) if desc is not None else None,
+    rc = load().stego_augment_check_params(_desc_ref(desc),
                                            ctypes.addressof(records) if records is not None else None, byref(bad), byref(contrast))
     return int(rc), int(bad.value), bool(contrast.value)
 
@@ -1788,16 +1771,14 @@ def augment_workspace_bytes(desc):
 
 def augment_plan(desc):
     """stego_augment_plan (host only) -> (return code, [(LDS bytes, workgroups) of the mean and the apply launch])."""
-    lds, wgs = (c_size_t * AUG_LAUNCHES)(), (c_int64 * AUG_LAUNCHES)()
-    rc = load().stego_augment_plan(byref(desc), lds, wgs)
-    return int(rc), [(int(a), int(b)) for a, b in zip(lds, wgs)]
+    return _launch_plan(load().stego_augment_plan, desc, AUG_LAUNCHES)
 
 
 def augment_raw(desc, img, params_host, params, img_aug, coord_aug, workspace, workspace_bytes, stream=None):
     """stego_augment with every argument given: `img` a StegoMap (or None), `params_host` a ctypes array of StegoAugParams, a raw
     address or None, the rest raw addresses or tensors (tests: the error codes) -> the return code, unchecked."""
     host = ctypes.addressof(params_host) if isinstance(params_host, ctypes.Array) else params_host
-    return int(load().stego_augment(byref(desc) if desc is not None else None, _ref(img), host, _addr(params), _addr(img_aug),
+    return int(load().stego_augment(_desc_ref(desc), _ref(img), host, _addr(params), _addr(img_aug),
                                     _addr(coord_aug), _addr(workspace), int(workspace_bytes), stream if stream is not None else None))
 
 
@@ -1842,15 +1823,13 @@ def aug_align_workspace_bytes(desc):
 
 def aug_align_plan(desc):
     """stego_aug_align_plan (host only) -> (return code, [(LDS bytes, workgroups) of the pixels and the finish launch])."""
-    lds, wgs = (c_size_t * AUGALIGN_LAUNCHES)(), (c_int64 * AUGALIGN_LAUNCHES)()
-    rc = load().stego_aug_align_plan(byref(desc), lds, wgs)
-    return int(rc), [(int(a), int(b)) for a, b in zip(lds, wgs)]
+    return _launch_plan(load().stego_aug_align_plan, desc, AUGALIGN_LAUNCHES)
 
 
 def aug_align_raw(desc, code, code_aug, coord, loss, d_code, d_code_aug, workspace, workspace_bytes, stream=None):
     """stego_aug_align with every argument given: the four maps are StegoMap (or None), the rest raw addresses or tensors (tests: the
     error codes) -> the return code, unchecked."""
-    return int(load().stego_aug_align(byref(desc) if desc is not None else None, _ref(code), _ref(code_aug), _addr(coord), _addr(loss),
+    return int(load().stego_aug_align(_desc_ref(desc), _ref(code), _ref(code_aug), _addr(coord), _addr(loss),
                                       _ref(d_code), _ref(d_code_aug), _addr(workspace), int(workspace_bytes),
                                       stream if stream is not None else None))
 
@@ -1893,15 +1872,13 @@ def rec_loss_workspace_bytes(desc):
 
 def rec_loss_plan(desc):
     """stego_rec_loss_plan (host only) -> (return code, [(LDS bytes, workgroups) of the tiles and the finish launch])."""
-    lds, wgs = (c_size_t * REC_LAUNCHES)(), (c_int64 * REC_LAUNCHES)()
-    rc = load().stego_rec_loss_plan(byref(desc), lds, wgs)
-    return int(rc), [(int(a), int(b)) for a, b in zip(lds, wgs)]
+    return _launch_plan(load().stego_rec_loss_plan, desc, REC_LAUNCHES)
 
 
 def rec_loss_raw(desc, code, feats, weight, bias, loss, d_code, d_weight, d_bias, workspace, workspace_bytes, stream=None):
     """stego_rec_loss with every argument given: `code`, `feats` and `d_code` are StegoMap (or None), the rest raw addresses or
     tensors (tests: the error codes) -> the return code, unchecked."""
-    return int(load().stego_rec_loss(byref(desc) if desc is not None else None, _ref(code), _ref(feats), _addr(weight), _addr(bias),
+    return int(load().stego_rec_loss(_desc_ref(desc), _ref(code), _ref(feats), _addr(weight), _addr(bias),
                                      _addr(loss), _ref(d_code), _addr(d_weight), _addr(d_bias), _addr(workspace), int(workspace_bytes),
                                      stream if stream is not None else None))
 

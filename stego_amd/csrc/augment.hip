@@ -24,6 +24,7 @@
 #include <cstdint>
 
 #include "../../include/stego_aug.h"
+#include "addon_device.h"
 #include "host_util.h"
 #include "probe_common.h"
 
@@ -155,13 +156,8 @@ __global__ __launch_bounds__(TPB) void aug_mean(AugP p)
         apply_ops(v, rec, ci, 0.f);
         s += gray3(v);
     }
-    red[t] = (double)s;
-    __syncthreads();
-    for (int m = TPB / 2; m > 0; m >>= 1) {
-        if (t < m) red[t] += red[t + m];
-        __syncthreads();
-    }
-    if (t == 0) p.part[(size_t)b * p.nblk + blk] = red[0];
+    const double sum = block_sum<TPB>((double)s, red);
+    if (t == 0) p.part[(size_t)b * p.nblk + blk] = sum;
 }
 
 // index -1 -> 1, -2 -> 2, R -> R - 2, R + 1 -> R - 3; positions further out (tile rows past the image) are never used: clamped
@@ -293,13 +289,6 @@ struct AlignP {
     long long npix;
 };
 
-__device__ inline float wave_sum(float v)
-{
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);        // the same tree in all 64 lanes
-    return v;
-}
-
 __global__ __launch_bounds__(TPB) void align_pixels(AlignP p)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -371,13 +360,8 @@ __global__ __launch_bounds__(TPB) void align_finish(AlignP p, int cell_blocks, i
     if ((int)blockIdx.x >= workers) {                    // the loss: the last block of the grid
         double s = 0.0;
         for (long long i = t; i < p.npix; i += TPB) s += (double)p.part[i];
-        red[t] = s;
-        __syncthreads();
-        for (int m = TPB / 2; m > 0; m >>= 1) {
-            if (t < m) red[t] += red[t + m];
-            __syncthreads();
-        }
-        if (t == 0) p.loss[0] = (float)(-red[0] / (double)p.npix);
+        s = block_sum<TPB>(s, red);
+        if (t == 0) p.loss[0] = (float)(-s / (double)p.npix);
         return;
     }
     // the (image, block of 16 cells) units, image-major, walked with the stride of the bounded grid; four cells per wave
@@ -431,7 +415,6 @@ __global__ __launch_bounds__(TPB) void align_finish(AlignP p, int cell_blocks, i
 
 using stego::aligned;
 using stego::hip_rc;
-inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 int check_aug(const StegoAugDesc* d)
 {
@@ -484,7 +467,9 @@ int check_records(const StegoAugDesc* d, const StegoAugParams* recs, int64_t* ba
 
 struct AugPlan {
     int nblk, tiles_x, tiles_y;
-    size_t ws_bytes;
+    size_t lds[STEGO_AUG_LAUNCHES];
+    int64_t wgs[STEGO_AUG_LAUNCHES];
+    size_t off_part, ws_bytes;
 };
 
 AugPlan aug_plan(const StegoAugDesc* d)
@@ -493,7 +478,13 @@ AugPlan aug_plan(const StegoAugDesc* d)
     pl.nblk = (d->R + MEAN_ROWS - 1) / MEAN_ROWS;
     pl.tiles_x = (d->R + TW - 1) / TW;
     pl.tiles_y = (d->R + TH - 1) / TH;
-    pl.ws_bytes = up16((size_t)d->B * pl.nblk * sizeof(double));
+    pl.lds[0] = TPB * sizeof(double);
+    pl.wgs[0] = (int64_t)d->B * pl.nblk;
+    pl.lds[1] = (size_t)(3 * HH * HW + 3 * HH * TW + 1) * sizeof(float);
+    pl.wgs[1] = (int64_t)d->B * pl.tiles_x * pl.tiles_y;
+    stego::WsLayout ws;
+    pl.off_part = ws.take((size_t)d->B * pl.nblk * sizeof(double), 16);
+    pl.ws_bytes = ws.total(16);
     return pl;
 }
 
@@ -511,6 +502,8 @@ int check_align(const StegoAugAlignDesc* d)
 struct AlignPlan {
     long long npix;
     int cell_blocks, workers;
+    size_t lds[STEGO_AUGALIGN_LAUNCHES];
+    int64_t wgs[STEGO_AUGALIGN_LAUNCHES];
     size_t off_part, off_tcell, off_tw, off_dA, ws_bytes;
 };
 
@@ -520,16 +513,15 @@ AlignPlan align_plan(const StegoAugAlignDesc* d)
     pl.npix = (long long)d->B * d->S * d->S;
     pl.cell_blocks = (d->h * d->w + FIN_CELLS - 1) / FIN_CELLS;
     pl.workers = (int)std::min<long long>((long long)pl.cell_blocks * d->B, FIN_MAX_WG);
-    size_t o = 0;
-    pl.off_part = o;
-    o = up16(o + (size_t)pl.npix * 4);
-    pl.off_tcell = o;
-    o = up16(o + (size_t)pl.npix * 16);
-    pl.off_tw = o;
-    o = up16(o + (size_t)pl.npix * 16);
-    pl.off_dA = o;
-    o = up16(o + (size_t)pl.npix * d->K * 4);
-    pl.ws_bytes = o;
+    pl.wgs[0] = (pl.npix + TPB / 64 - 1) / (TPB / 64);
+    pl.lds[1] = TPB * sizeof(double);
+    pl.wgs[1] = (int64_t)pl.workers + 1;
+    stego::WsLayout ws;
+    pl.off_part = ws.take((size_t)pl.npix * 4, 16);
+    pl.off_tcell = ws.take((size_t)pl.npix * 16, 16);
+    pl.off_tw = ws.take((size_t)pl.npix * 16, 16);
+    pl.off_dA = ws.take((size_t)pl.npix * d->K * 4, 16);
+    pl.ws_bytes = ws.total(16);
     return pl;
 }
 
@@ -549,20 +541,9 @@ extern "C" size_t stego_augment_workspace_bytes(const StegoAugDesc* desc)
 extern "C" int stego_augment_plan(const StegoAugDesc* desc, size_t lds_bytes[STEGO_AUG_LAUNCHES], int64_t workgroups[STEGO_AUG_LAUNCHES])
 {
     const int rc = check_aug(desc);
-    size_t lds[STEGO_AUG_LAUNCHES] = {0, 0};
-    int64_t wgs[STEGO_AUG_LAUNCHES] = {0, 0};
-    if (rc == STEGO_OK) {
-        const AugPlan pl = aug_plan(desc);
-        lds[0] = TPB * sizeof(double);
-        wgs[0] = (int64_t)desc->B * pl.nblk;
-        lds[1] = (size_t)(3 * HH * HW + 3 * HH * TW + 1) * sizeof(float);
-        wgs[1] = (int64_t)desc->B * pl.tiles_x * pl.tiles_y;
-    }
-    for (int i = 0; i < STEGO_AUG_LAUNCHES; ++i) {
-        if (lds_bytes) lds_bytes[i] = lds[i];
-        if (workgroups) workgroups[i] = wgs[i];
-    }
-    return rc;
+    AugPlan pl{};
+    if (rc == STEGO_OK) pl = aug_plan(desc);
+    return stego::report_plan(rc, STEGO_AUG_LAUNCHES, pl.lds, pl.wgs, lds_bytes, workgroups);
 }
 
 extern "C" int stego_augment(const StegoAugDesc* desc, const StegoMap* img, const StegoAugParams* params_host, const StegoAugParams* params,
@@ -584,21 +565,19 @@ extern "C" int stego_augment(const StegoAugDesc* desc, const StegoMap* img, cons
     p.params = params;
     p.img_aug = img_aug;
     p.coord_aug = coord_aug;
-    p.part = static_cast<double*>(workspace);
+    p.part = stego::at<double>(workspace, pl.off_part);
     p.B = desc->B;
     p.H = desc->H;
     p.W = desc->W;
     p.R = desc->R;
     p.nblk = pl.nblk;
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    (void)hipGetLastError();
-    if (any_contrast) {
-        aug_mean<<<dim3((unsigned)pl.nblk, (unsigned)desc->B), TPB, 0, s>>>(p);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_rc(e);
-    }
-    aug_apply<<<dim3((unsigned)pl.tiles_x, (unsigned)pl.tiles_y, (unsigned)desc->B), TPB, 0, s>>>(p, desc->R % 4 == 0 ? 1 : 0);
-    return hip_rc(hipGetLastError());
+    const dim3 tiles((unsigned)pl.tiles_x, (unsigned)pl.tiles_y, (unsigned)desc->B);
+    const int vec4 = desc->R % 4 == 0 ? 1 : 0;
+    if (!any_contrast) return hip_rc(stego::launch_first<aug_apply>(tiles, TPB, 0, s, p, vec4));
+    const hipError_t e = stego::launch_first<aug_mean>(dim3((unsigned)pl.nblk, (unsigned)desc->B), TPB, 0, s, p);
+    if (e != hipSuccess) return hip_rc(e);
+    return hip_rc(stego::launch_next<aug_apply>(tiles, TPB, 0, s, p, vec4));
 }
 
 extern "C" size_t stego_aug_align_workspace_bytes(const StegoAugAlignDesc* desc)
@@ -610,19 +589,9 @@ extern "C" int stego_aug_align_plan(const StegoAugAlignDesc* desc, size_t lds_by
                                     int64_t workgroups[STEGO_AUGALIGN_LAUNCHES])
 {
     const int rc = check_align(desc);
-    size_t lds[STEGO_AUGALIGN_LAUNCHES] = {0, 0};
-    int64_t wgs[STEGO_AUGALIGN_LAUNCHES] = {0, 0};
-    if (rc == STEGO_OK) {
-        const AlignPlan pl = align_plan(desc);
-        wgs[0] = (pl.npix + TPB / 64 - 1) / (TPB / 64);
-        lds[1] = TPB * sizeof(double);
-        wgs[1] = (int64_t)pl.workers + 1;
-    }
-    for (int i = 0; i < STEGO_AUGALIGN_LAUNCHES; ++i) {
-        if (lds_bytes) lds_bytes[i] = lds[i];
-        if (workgroups) workgroups[i] = wgs[i];
-    }
-    return rc;
+    AlignPlan pl{};
+    if (rc == STEGO_OK) pl = align_plan(desc);
+    return stego::report_plan(rc, STEGO_AUGALIGN_LAUNCHES, pl.lds, pl.wgs, lds_bytes, workgroups);
 }
 
 extern "C" int stego_aug_align(const StegoAugAlignDesc* desc, const StegoMap* code, const StegoMap* code_aug, const float* coord,
@@ -640,7 +609,7 @@ extern "C" int stego_aug_align(const StegoAugAlignDesc* desc, const StegoMap* co
         (d_code && !aligned(d_code->data, 4)) || (d_code_aug && !aligned(d_code_aug->data, 4)) || !aligned(workspace, 16))
         return STEGO_ERR_ALIGN;
 
-    char* ws = static_cast<char*>(workspace);
+    using stego::at;
     AlignP p{};
     p.code = *code;
     p.caug = *code_aug;
@@ -648,10 +617,10 @@ extern "C" int stego_aug_align(const StegoAugAlignDesc* desc, const StegoMap* co
     if (d_code_aug) p.dcaug = *d_code_aug;
     p.coord = coord;
     p.loss = loss;
-    p.part = reinterpret_cast<float*>(ws + pl.off_part);
-    p.tcell = reinterpret_cast<int*>(ws + pl.off_tcell);
-    p.tw = reinterpret_cast<float*>(ws + pl.off_tw);
-    p.dA = reinterpret_cast<float*>(ws + pl.off_dA);
+    p.part = at<float>(workspace, pl.off_part);
+    p.tcell = at<int>(workspace, pl.off_tcell);
+    p.tw = at<float>(workspace, pl.off_tw);
+    p.dA = at<float>(workspace, pl.off_dA);
     p.B = desc->B;
     p.K = desc->K;
     p.h = desc->h;
@@ -667,12 +636,9 @@ extern "C" int stego_aug_align(const StegoAugAlignDesc* desc, const StegoMap* co
     p.npix = pl.npix;
 
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    (void)hipGetLastError();
-    align_pixels<<<(unsigned)((pl.npix + TPB / 64 - 1) / (TPB / 64)), TPB, 0, s>>>(p);
-    const hipError_t e = hipGetLastError();
+    const hipError_t e = stego::launch_first<align_pixels>((unsigned)pl.wgs[0], TPB, 0, s, p);
     if (e != hipSuccess) return hip_rc(e);
     // the (image, 16 cells) units of the transpose on a bounded grid (none without d_code), and one more block for the loss
     const int workers = d_code ? pl.workers : 0;
-    align_finish<<<(unsigned)workers + 1, TPB, 0, s>>>(p, pl.cell_blocks, workers);
-    return hip_rc(hipGetLastError());
+    return hip_rc(stego::launch_next<align_finish>((unsigned)workers + 1, TPB, 0, s, p, pl.cell_blocks, workers));
 }

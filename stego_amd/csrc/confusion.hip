@@ -246,11 +246,10 @@ extern "C" int stego_probe_confusion(const StegoProbeConfusionDesc* desc, const 
     int rc = check_desc(desc);
     if (rc != STEGO_OK) return rc;
     const bool lin = desc->lin_on != 0, clu = desc->clu_on != 0;
-    if (!code || !code->data || (code_flip && !code_flip->data) || !labels) return STEGO_ERR_NULL;
-    if ((lin && (!lin_w || !lin_b || !lin_counts)) || (clu && (!centroids || !clu_counts))) return STEGO_ERR_NULL;
-    if (!aligned(code->data, 4) || (code_flip && !aligned(code_flip->data, 4)) || !aligned(labels, 8)) return STEGO_ERR_ALIGN;
-    if (lin && (!aligned(lin_w, 4) || !aligned(lin_b, 4) || !aligned(lin_counts, 8))) return STEGO_ERR_ALIGN;
-    if (clu && (!aligned(centroids, 4) || !aligned(clu_counts, 8))) return STEGO_ERR_ALIGN;
+    if (!labels) return STEGO_ERR_NULL;                 // (with the other NULL tests: a NULL anywhere comes before an alignment)
+    rc = check_probe_ptrs(code, code_flip, lin, lin_w, lin_b, lin_counts, 8, clu, centroids, clu_counts, 8);
+    if (rc != STEGO_OK) return rc;
+    if (!aligned(labels, 8)) return STEGO_ERR_ALIGN;
 
     const TilePlan pl = plan(desc);
     if (pl.lds > LDS_BUDGET) return STEGO_ERR_UNSUPPORTED;          // (unreachable: a 1 x 1 tile's footprint and both histograms fit)
@@ -287,16 +286,7 @@ extern "C" int stego_probe_confusion(const StegoProbeConfusionDesc* desc, const 
     const int64_t tiles = (int64_t)p.tpi * desc->B;
     const unsigned grid = (unsigned)std::min(tiles, std::max((int64_t)stego::device_cu_count() * WGS_PER_CU, tiles * TPB / MAX_WG_PIXELS + 1));
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    (void)hipGetLastError();
-    if (pl.NMAX == 8)
-        probe_confusion_kernel<8><<<grid, TPB, pl.lds, s>>>(p);
-    else if (pl.NMAX == 16)
-        probe_confusion_kernel<16><<<grid, TPB, pl.lds, s>>>(p);
-    else if (pl.NMAX == 32)
-        probe_confusion_kernel<32><<<grid, TPB, pl.lds, s>>>(p);
-    else
-        probe_confusion_kernel<64><<<grid, TPB, pl.lds, s>>>(p);
-    return hip_rc(hipGetLastError());
+    return hip_rc(stego::with_const<8, 16, 32, 64>(pl.NMAX, [&](auto N) { return stego::launch_first<probe_confusion_kernel<N()>>(grid, TPB, pl.lds, s, p); }));
 }
 
 extern "C" int stego_confusion(const StegoConfusionDesc* desc, const void* pred, const int64_t* labels, int64_t* counts,
@@ -322,10 +312,6 @@ extern "C" int stego_confusion(const StegoConfusionDesc* desc, const void* pred,
     const int64_t rounds = (p.total + TPB - 1) / TPB;
     const unsigned grid = (unsigned)std::min(rounds, std::max((int64_t)stego::device_cu_count() * WGS_PER_CU, p.total / MAX_WG_PIXELS + 1));
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    (void)hipGetLastError();
-    if (scores)
-        confusion_count_kernel<true><<<grid, TPB, 0, s>>>(p);
-    else
-        confusion_count_kernel<false><<<grid, TPB, 0, s>>>(p);
-    return hip_rc(hipGetLastError());
+    if (scores) return hip_rc(stego::launch_first<confusion_count_kernel<true>>(grid, TPB, 0, s, p));
+    return hip_rc(stego::launch_first<confusion_count_kernel<false>>(grid, TPB, 0, s, p));
 }

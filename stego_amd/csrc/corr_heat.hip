@@ -25,6 +25,7 @@
 #include <cstdint>
 
 #include "../../include/stego_heat.h"
+#include "addon_device.h"
 #include "corr_tile.h"
 #include "host_util.h"
 
@@ -71,33 +72,6 @@ struct WriteParams {
     float sy, sx;
     int32_t h, w, hw, N, NCH, H, W, RB, flags, cap_rows;
 };
-
-// ATen grid_sampler_2d (bilinear, border, align_corners=True), as corr_pr.hip computes it
-struct Taps {
-    int x0, y0, x1, y1;
-    float wx0, wx1, wy0, wy1;
-};
-
-__device__ __forceinline__ Taps bilinear_taps(float x, float y, int H, int W)
-{
-    float ix = ((x + 1.f) * 0.5f) * (float)(W - 1);
-    float iy = ((y + 1.f) * 0.5f) * (float)(H - 1);
-    ix = fminf((float)(W - 1), fmaxf(ix, 0.f));
-    iy = fminf((float)(H - 1), fmaxf(iy, 0.f));
-    const float fx0 = floorf(ix), fy0 = floorf(iy);
-    Taps t;
-    t.x0 = (int)fx0;
-    t.y0 = (int)fy0;
-    t.x1 = t.x0 + 1;
-    t.y1 = t.y0 + 1;
-    t.wx1 = ix - fx0;
-    t.wx0 = (fx0 + 1.f) - ix;
-    t.wy1 = iy - fy0;
-    t.wy0 = (fy0 + 1.f) - iy;
-    if (t.x1 > W - 1) { t.wx1 = 0.f; t.x1 = t.x0; }      // out-of-range taps contribute zero
-    if (t.y1 > H - 1) { t.wy1 = 0.f; t.y1 = t.y0; }
-    return t;
-}
 
 __global__ __launch_bounds__(NTHREADS) void heat_low_kernel(LowParams p)
 {
@@ -370,7 +344,7 @@ int check_desc(const StegoHeatDesc* d)
 struct Plan {
     int NCH, NT, RB, blocks, span, V;
     float sy, sx;
-    size_t off_low, off_pmax, off_pidx, ws_bytes, lds2;
+    size_t off_psum, off_low, off_pmax, off_pidx, ws_bytes, lds2;
 };
 
 // torch's area_pixel_compute_scale under align_corners=True
@@ -412,14 +386,12 @@ Plan plan(const StegoHeatDesc* d, bool vec_ok)
     pl.span = max_span(d, pl.sy, pl.RB);             // RB == 1: at most two rows, and 2 * w <= h * w <= 16384 when h >= 2
     pl.blocks = (d->H + pl.RB - 1) / pl.RB;
     pl.lds2 = (size_t)pl.span * d->w * 4;
-    size_t o = (size_t)rows * pl.NCH * 8;
-    pl.off_low = o;
-    o += (size_t)rows * hw * 4;
-    pl.off_pmax = o;
-    o += (size_t)rows * pl.NCH * 4;
-    pl.off_pidx = o;
-    o += (size_t)rows * pl.NCH * 4;
-    pl.ws_bytes = (o + 7) & ~(size_t)7;
+    WsLayout ws;                                     // packed tight: the fp64 sums come first, everything after them is 4-byte data
+    pl.off_psum = ws.take((size_t)rows * pl.NCH * 8, 1);
+    pl.off_low = ws.take((size_t)rows * hw * 4, 1);
+    pl.off_pmax = ws.take((size_t)rows * pl.NCH * 4, 1);
+    pl.off_pidx = ws.take((size_t)rows * pl.NCH * 4, 1);
+    pl.ws_bytes = ws.total(8);
     return pl;
 }
 
@@ -454,16 +426,15 @@ extern "C" int stego_corr_heatmaps(const StegoHeatDesc* desc, const StegoMap* sr
         return STEGO_ERR_ALIGN;
     if (!aligned(index_t, 8) || !aligned(workspace, 8)) return STEGO_ERR_ALIGN;
 
-    char* const ws = static_cast<char*>(workspace);
     LowParams lp{};
     lp.src = *src;
     lp.tgt = *tgt;
     lp.index_t = index_t;
     lp.points = points;
-    lp.psum = reinterpret_cast<double*>(ws);
-    lp.low = reinterpret_cast<float*>(ws + pl.off_low);
-    lp.pmax = reinterpret_cast<float*>(ws + pl.off_pmax);
-    lp.pidx = reinterpret_cast<int32_t*>(ws + pl.off_pidx);
+    lp.psum = at<double>(workspace, pl.off_psum);
+    lp.low = at<float>(workspace, pl.off_low);
+    lp.pmax = at<float>(workspace, pl.off_pmax);
+    lp.pidx = at<int32_t>(workspace, pl.off_pidx);
     lp.B = desc->B;
     lp.C = desc->C;
     lp.hs = desc->hs;
@@ -502,9 +473,5 @@ extern "C" int stego_corr_heatmaps(const StegoHeatDesc* desc, const StegoMap* sr
     const hipError_t e = launch<heat_low_kernel>(dim3((unsigned)pl.NCH, (unsigned)pl.NT, (unsigned)desc->B), dim3(NTHREADS), (int)LOW_LDS_BYTES, s, lp);
     if (e != hipSuccess) return hip_rc(e);
     const dim3 grid2((unsigned)pl.blocks, (unsigned)desc->N, (unsigned)desc->B);
-    if (pl.V == 4)
-        heat_write_kernel<4><<<grid2, NTHREADS, pl.lds2, s>>>(wp);
-    else
-        heat_write_kernel<1><<<grid2, NTHREADS, pl.lds2, s>>>(wp);
-    return hip_rc(hipGetLastError());
+    return hip_rc(with_const<4, 1>(pl.V, [&](auto V) { return launch_next<heat_write_kernel<V()>>(grid2, NTHREADS, pl.lds2, s, wp); }));
 }

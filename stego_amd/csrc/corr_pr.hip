@@ -22,6 +22,7 @@
 #include <cstdint>
 
 #include "../../include/stego_pr.h"
+#include "addon_device.h"
 #include "corr_tile.h"
 #include "host_util.h"
 
@@ -55,34 +56,6 @@ struct PrParams {
     unsigned long long* hist;
     int32_t B, C, h, w, HL, WL, N1, N2, n_bins, n_classes, flags, NCH;
 };
-
-// ATen grid_sampler_2d (bilinear, border, align_corners=True) as corr_common.h's make_taps computes it, with the factors of the four
-// weights kept apart (the label test needs to know which taps have a non-zero weight) and no 16-bit packing of the pixel.
-struct Taps {
-    int x0, y0, x1, y1;
-    float wx0, wx1, wy0, wy1;
-};
-
-__device__ __forceinline__ Taps bilinear_taps(float x, float y, int H, int W)
-{
-    float ix = ((x + 1.f) * 0.5f) * (float)(W - 1);
-    float iy = ((y + 1.f) * 0.5f) * (float)(H - 1);
-    ix = fminf((float)(W - 1), fmaxf(ix, 0.f));
-    iy = fminf((float)(H - 1), fmaxf(iy, 0.f));
-    const float fx0 = floorf(ix), fy0 = floorf(iy);
-    Taps t;
-    t.x0 = (int)fx0;
-    t.y0 = (int)fy0;
-    t.x1 = t.x0 + 1;
-    t.y1 = t.y0 + 1;
-    t.wx1 = ix - fx0;
-    t.wx0 = (fx0 + 1.f) - ix;
-    t.wy1 = iy - fy0;
-    t.wy0 = (fy0 + 1.f) - iy;
-    if (t.x1 > W - 1) { t.wx1 = 0.f; t.x1 = t.x0; }      // out-of-range taps contribute zero
-    if (t.y1 > H - 1) { t.wy1 = 0.f; t.y1 = t.y0; }
-    return t;
-}
 
 // One side's 64-channel chunk of 128 sampled points -> float stage[128][LDA].  Wave `wave` takes points wave, wave + 4, ...
 __device__ __forceinline__ void sample_chunk(const float* __restrict__ lane_base, bool chok, const long long* __restrict__ tapo,

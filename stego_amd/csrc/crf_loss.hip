@@ -27,6 +27,7 @@
 #include <cstdint>
 
 #include "../../include/stego_crf_loss.h"
+#include "addon_device.h"
 #include "host_util.h"
 #include "probe_common.h"
 
@@ -152,9 +153,6 @@ __global__ __launch_bounds__(PREP_TPB) void crf_prepare(CrfParams p)
     }
 }
 
-// row b of a 32 x 32 accumulator tile that register r of lane half hf holds (the C / D layout of the 32x32 matrix instructions)
-__device__ inline int acc_row(int r, int hf) { return (r & 3) + 8 * (r >> 2) + 4 * hf; }
-
 template <int NT, bool BWD>
 __global__ __launch_bounds__(PAIR_TPB, 2) void crf_pairs(CrfParams p)
 {
@@ -246,19 +244,14 @@ __global__ __launch_bounds__(PAIR_TPB, 2) void crf_pairs(CrfParams p)
     }
 
     __syncthreads();                                    // every wave is past its last read of the stage
-    red[t] = lsum;
     if (BWD && cw == 1) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) xs[(rw * 32 + acc_row(r, hf)) * KP + nt * 32 + li] = pacc[nt][r];
     }
-    __syncthreads();
-    for (int s = PAIR_TPB / 2; s > 0; s >>= 1) {
-        if (t < s) red[t] += red[t + s];
-        __syncthreads();
-    }
-    if (t == 0) p.part[blockIdx.x] = red[0];
+    const double wg_sum = block_sum<PAIR_TPB>(lsum, red);
+    if (t == 0) p.part[blockIdx.x] = wg_sum;
     if (!BWD || cw == 1) return;
 
     float dot[16];
@@ -317,13 +310,8 @@ __global__ __launch_bounds__(FIN_TPB) void crf_finish(CrfParams p, int cell_bloc
             if (p.per_image) p.per_image[b] = (float)(-s / n2);
             tot += s;
         }
-        red[t] = tot;
-        __syncthreads();
-        for (int s = FIN_TPB / 2; s > 0; s >>= 1) {
-            if (t < s) red[t] += red[t + s];
-            __syncthreads();
-        }
-        if (t == 0) p.loss[0] = (float)(-red[0] / (n2 * (double)p.B));
+        tot = block_sum<FIN_TPB>(tot, red);
+        if (t == 0) p.loss[0] = (float)(-tot / (n2 * (double)p.B));
         return;
     }
     // the (image, block of 16 cells) units, image-major, walked with the stride of the bounded grid
@@ -380,8 +368,6 @@ struct Plan {
     size_t off_keys, off_tw, off_part, off_xh, off_P, off_pt, off_nrm, ws_bytes;
 };
 
-inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 Plan plan(const StegoCrfLossDesc* d)
 {
     Plan pl{};
@@ -400,42 +386,22 @@ Plan plan(const StegoCrfLossDesc* d)
     pl.fin_workers = (int)std::min<int64_t>((int64_t)pl.cell_blocks * d->B, FIN_MAX_WG);
     pl.wgs[2] = pl.fin_workers + 1;
     const size_t rows = (size_t)d->B * pl.Np;
-    size_t o = 0;
-    pl.off_keys = o;
-    o = up16(o + (size_t)pl.T4p * 8);
-    pl.off_tw = o;
-    o = up16(o + (size_t)4 * d->N * 4);
-    pl.off_part = o;
-    o = up16(o + (size_t)d->B * pl.n_rowblk * 8);
-    pl.off_xh = o;
-    o = up16(o + rows * pl.KP * 4);
-    pl.off_P = o;
-    o = up16(o + rows * pl.KP * 4);
-    pl.off_pt = o;
-    o = up16(o + rows * PS * 4);
-    pl.off_nrm = o;
-    o = up16(o + rows * 2 * 4);
-    pl.ws_bytes = o;
+    stego::WsLayout ws;
+    pl.off_keys = ws.take((size_t)pl.T4p * 8, 16);
+    pl.off_tw = ws.take((size_t)4 * d->N * 4, 16);
+    pl.off_part = ws.take((size_t)d->B * pl.n_rowblk * 8, 16);
+    pl.off_xh = ws.take(rows * pl.KP * 4, 16);
+    pl.off_P = ws.take(rows * pl.KP * 4, 16);
+    pl.off_pt = ws.take(rows * PS * 4, 16);
+    pl.off_nrm = ws.take(rows * 2 * 4, 16);
+    pl.ws_bytes = ws.total(16);
     return pl;
-}
-
-template <int NT, bool BWD>
-hipError_t launch_pairs_as(const CrfParams& p, unsigned grid, size_t lds, hipStream_t s)
-{
-    constexpr auto kernel = &crf_pairs<NT, BWD>;        // (named once: the attribute and the launch mean the same instantiation)
-    if (lds > 64 * 1024) {                              // beyond the default limit of dynamic LDS
-        const hipError_t e = stego::allow_dynamic_lds<kernel>((int)lds);
-        if (e != hipSuccess) return e;
-    }
-    (void)hipGetLastError();
-    kernel<<<grid, PAIR_TPB, lds, s>>>(p);
-    return hipGetLastError();
 }
 
 template <bool BWD>
 hipError_t launch_pairs(int NT, const CrfParams& p, unsigned grid, size_t lds, hipStream_t s)
 {
-    return stego::with_const<1, 2, 3, 4>(NT, [&](auto N) { return launch_pairs_as<N(), BWD>(p, grid, lds, s); });      // (anything else: 4)
+    return stego::with_const<1, 2, 3, 4>(NT, [&](auto N) { return stego::launch_first<crf_pairs<N(), BWD>>(grid, PAIR_TPB, lds, s, p); });      // (anything else: 4)
 }
 
 }  // namespace
@@ -451,11 +417,7 @@ extern "C" int stego_crf_loss_plan(const StegoCrfLossDesc* desc, size_t lds_byte
     const int rc = check_desc(desc);
     Plan pl{};
     if (rc == STEGO_OK) pl = plan(desc);
-    for (int i = 0; i < STEGO_CRFLOSS_LAUNCHES; ++i) {
-        if (lds_bytes) lds_bytes[i] = pl.lds[i];
-        if (workgroups) workgroups[i] = pl.wgs[i];
-    }
-    return rc;
+    return stego::report_plan(rc, STEGO_CRFLOSS_LAUNCHES, pl.lds, pl.wgs, lds_bytes, workgroups);
 }
 
 extern "C" int stego_crf_loss(const StegoCrfLossDesc* desc, const StegoMap* guidance, const StegoMap* code, const int64_t* coords,
@@ -472,19 +434,19 @@ extern "C" int stego_crf_loss(const StegoCrfLossDesc* desc, const StegoMap* guid
         (d_code && !aligned(d_code->data, 4)) || !aligned(workspace, 16))
         return STEGO_ERR_ALIGN;
 
-    char* ws = static_cast<char*>(workspace);
+    using stego::at;
     CrfParams p{};
     p.code = *code;
     p.guid = *guidance;
     if (d_code) p.dcode = *d_code;
     p.coords = coords;
-    p.keys = reinterpret_cast<unsigned long long*>(ws + pl.off_keys);
-    p.tw = reinterpret_cast<float*>(ws + pl.off_tw);
-    p.part = reinterpret_cast<double*>(ws + pl.off_part);
-    p.xh = reinterpret_cast<float*>(ws + pl.off_xh);
-    p.P = reinterpret_cast<float*>(ws + pl.off_P);
-    p.pt = reinterpret_cast<float*>(ws + pl.off_pt);
-    p.nrm = reinterpret_cast<float*>(ws + pl.off_nrm);
+    p.keys = at<unsigned long long>(workspace, pl.off_keys);
+    p.tw = at<float>(workspace, pl.off_tw);
+    p.part = at<double>(workspace, pl.off_part);
+    p.xh = at<float>(workspace, pl.off_xh);
+    p.P = at<float>(workspace, pl.off_P);
+    p.pt = at<float>(workspace, pl.off_pt);
+    p.nrm = at<float>(workspace, pl.off_nrm);
     p.loss = loss;
     p.per_image = per_image;
     p.B = desc->B;
@@ -516,19 +478,11 @@ extern "C" int stego_crf_loss(const StegoCrfLossDesc* desc, const StegoMap* guid
 
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t lds0 = d_code ? pl.lds[0] : 0;
-    constexpr auto prepare = &crf_prepare;
-    if (lds0 > 64 * 1024) {
-        const hipError_t e = stego::allow_dynamic_lds<prepare>((int)lds0);
-        if (e != hipSuccess) return hip_rc(e);
-    }
-    (void)hipGetLastError();
-    prepare<<<(unsigned)(pl.wgs[0] - (d_code ? 0 : 1)), PREP_TPB, lds0, s>>>(p);
-    hipError_t e = hipGetLastError();
+    hipError_t e = stego::launch_first<crf_prepare>((unsigned)(pl.wgs[0] - (d_code ? 0 : 1)), PREP_TPB, lds0, s, p);
     if (e != hipSuccess) return hip_rc(e);
     e = d_code ? launch_pairs<true>(pl.NT, p, (unsigned)pl.wgs[1], pl.lds[1], s) : launch_pairs<false>(pl.NT, p, (unsigned)pl.wgs[1], pl.lds[1], s);
     if (e != hipSuccess) return hip_rc(e);
     // the (image, 16 cells) units of the unsample on a bounded grid (none without a gradient), and one more block for the loss
     const int workers = d_code ? pl.fin_workers : 0;
-    crf_finish<<<(unsigned)workers + 1, FIN_TPB, 0, s>>>(p, pl.cell_blocks, workers);
-    return hip_rc(hipGetLastError());
+    return hip_rc(stego::launch_next<crf_finish>((unsigned)workers + 1, FIN_TPB, 0, s, p, pl.cell_blocks, workers));
 }

@@ -1,5 +1,5 @@
-// Host-side helpers shared by the launchers: a HIP error as a C-ABI return code, the pointer alignment test, per-device caches
-// (thread-safe), environment knobs read once.
+// Host-side helpers shared by the launchers: a HIP error as a C-ABI return code, the pointer alignment test, the launch helpers, what an
+// array-style *_plan export reports, per-device caches (thread-safe), environment knobs read once.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +8,7 @@
 
 #include "../../include/stego_corr.h"
 #include "dispatch.h"
+#include "ws_layout.h"
 
 namespace stego {
 
@@ -24,7 +25,7 @@ hipError_t ensure_dynamic_lds(const void* kernel, int bytes);
 // One launch of one instantiation: the dynamic-LDS attribute (only when lds > 0), the launch, the runtime's answer to it.  The kernel is
 // named once, as the template argument, so the attribute and the launch cannot mean different instantiations.  (allow_dynamic_lds on its
 // own, where attribute and launch are not one to one: corr_wide.hip sets two kernels' attributes once, in front of a loop of launches;
-// crf_loss.hip and probe_train.hip set theirs only beyond the 64 KB that every kernel may use, and name the kernel once as a constant.)
+// the add-on units launch through launch_first / launch_next below, which set it only beyond the 64 KB that every kernel may use.)
 template <auto Kernel>
 inline hipError_t allow_dynamic_lds(int lds) { return lds > 0 ? ensure_dynamic_lds(reinterpret_cast<const void*>(Kernel), lds) : hipSuccess; }
 
@@ -35,6 +36,44 @@ inline hipError_t launch(dim3 grid, dim3 block, int lds, hipStream_t stream, con
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(Kernel, grid, block, lds, stream, args...);
     return hipGetLastError();
+}
+
+// The add-on units' launch (crf_loss, augment, rec_loss, corr_heat, corr_pr, the probe units, salience_draw, optim_step): the attribute
+// only beyond the 64 KB of dynamic LDS that every kernel may use, and launch_first clears what an earlier call left in the thread's
+// sticky error before it launches, so the answer is this launch's own.  launch_next is for a further launch of the same API call, right
+// after a launch that answered hipSuccess: there is nothing to clear.
+template <auto Kernel, class... Args>
+inline hipError_t launch_next(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const Args&... args)
+{
+    if (lds > 64 * 1024) {
+        const hipError_t e = allow_dynamic_lds<Kernel>((int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, stream, args...);
+    return hipGetLastError();
+}
+
+template <auto Kernel, class... Args>
+inline hipError_t launch_first(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const Args&... args)
+{
+    if (lds > 64 * 1024) {
+        const hipError_t e = allow_dynamic_lds<Kernel>((int)lds);
+        if (e != hipSuccess) return e;
+    }
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(Kernel, grid, block, lds, stream, args...);
+    return hipGetLastError();
+}
+
+// What an array-style *_plan export answers: the descriptor's return code, and per launch its LDS bytes and workgroups - zeros when the
+// descriptor is bad (lds / wgs are not read then).  Either output may be NULL.
+inline int report_plan(int rc, int n, const size_t* lds, const int64_t* wgs, size_t* lds_out, int64_t* wgs_out)
+{
+    for (int i = 0; i < n; ++i) {
+        if (lds_out) lds_out[i] = rc == STEGO_OK ? lds[i] : 0;
+        if (wgs_out) wgs_out[i] = rc == STEGO_OK ? wgs[i] : 0;
+    }
+    return rc;
 }
 
 // with_const (dispatch.h) for launchers that have no instantiation for an unlisted value

@@ -256,7 +256,5 @@ extern "C" int stego_adam_step(const StegoAdamDesc* desc, const StegoAdamSegment
     p.n_chunks = (int32_t)chunks;                                 // < 2^21 + 256
     p.zero = desc->zero_grads;
     for (int g = 0; g < STEGO_ADAM_MAX_GROUPS; ++g) p.groups[g] = desc->groups[g];
-    (void)hipGetLastError();
-    adam_step_kernel<<<grid_for(chunks), TPB, 0, static_cast<hipStream_t>(stream)>>>(p);
-    return hip_rc(hipGetLastError());
+    return hip_rc(stego::launch_first<adam_step_kernel>(grid_for(chunks), TPB, 0, static_cast<hipStream_t>(stream), p));
 }

@@ -1,6 +1,6 @@
 // What the fused probe kernels share (probe_head.hip, confusion.hip, probe_train.hip): torch's bilinear source index on the device and
-// on the host, the strided code load, an output tile's source footprint on the device and its largest extent on the host, and the host's
-// tile plan of the probe head and the probe-confusion kernel.  The device phases those two kernels are built from: probe_phases.h.
+// on the host, the strided code load, an output tile's source footprint on the device and its largest extent on the host, the host's
+// tile plan of the probe head and the probe-confusion kernel, and the pointer checks their launchers share.  The device phases those two kernels are built from: probe_phases.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "../../include/stego_corr.h"
+#include "host_util.h"
 
 namespace {
 
@@ -68,6 +69,22 @@ int max_span(int out, int in, float scale, int T)
         best = b - a + 1 > best ? b - a + 1 : best;
     }
     return best + 1 < in ? best + 1 : in;
+}
+
+// The pointer checks the probe head, the stitched probe head and the probe-confusion kernel share, in the order every one of them
+// keeps: the code maps, then a live probe's weights and output - all for NULL, then all for alignment (the output's alignment depends
+// on what is written there, so the caller names it).  STEGO_OK, STEGO_ERR_NULL or STEGO_ERR_ALIGN.
+inline int check_probe_ptrs(const StegoMap* code, const StegoMap* code_flip, bool lin, const float* lin_w, const float* lin_b,
+                            const void* lin_out, size_t lin_out_align, bool clu, const float* centroids, const void* clu_out,
+                            size_t clu_out_align)
+{
+    using stego::aligned;
+    if (!code || !code->data || (code_flip && !code_flip->data)) return STEGO_ERR_NULL;
+    if ((lin && (!lin_w || !lin_b || !lin_out)) || (clu && (!centroids || !clu_out))) return STEGO_ERR_NULL;
+    if (!aligned(code->data, 4) || (code_flip && !aligned(code_flip->data, 4))) return STEGO_ERR_ALIGN;
+    if (lin && (!aligned(lin_w, 4) || !aligned(lin_b, 4) || !aligned(lin_out, lin_out_align))) return STEGO_ERR_ALIGN;
+    if (clu && (!aligned(centroids, 4) || !aligned(clu_out, clu_out_align))) return STEGO_ERR_ALIGN;
+    return STEGO_OK;
 }
 
 // Label slots of a kernel instantiation: the probes' larger live label count n, rounded up to 8, 16, 32 or 64.

@@ -93,7 +93,6 @@ __global__ __launch_bounds__(TPB) void probe_head_kernel(ProbeParams p)
     }
 }
 
-using stego::aligned;
 using stego::hip_rc;
 
 inline bool kind_ok(int k) { return k >= STEGO_PROBE_SKIP && k <= STEGO_PROBE_ARGMAX; }
@@ -135,12 +134,9 @@ extern "C" int stego_probe_head(const StegoProbeDesc* desc, const StegoMap* code
     int rc = check_desc(desc);
     if (rc != STEGO_OK) return rc;
     const bool lin = desc->lin_kind != STEGO_PROBE_SKIP, clu = desc->clu_kind != STEGO_PROBE_SKIP;
-    if (!code || !code->data || (code_flip && !code_flip->data)) return STEGO_ERR_NULL;
-    if ((lin && (!lin_w || !lin_b || !lin_out)) || (clu && (!centroids || !clu_out))) return STEGO_ERR_NULL;
-    if (!aligned(code->data, 4) || (code_flip && !aligned(code_flip->data, 4))) return STEGO_ERR_ALIGN;
-    if (lin && (!aligned(lin_w, 4) || !aligned(lin_b, 4) || !aligned(lin_out, desc->lin_kind == STEGO_PROBE_ARGMAX ? 8 : 4)))
-        return STEGO_ERR_ALIGN;
-    if (clu && (!aligned(centroids, 4) || !aligned(clu_out, desc->clu_kind == STEGO_PROBE_ARGMAX ? 8 : 4))) return STEGO_ERR_ALIGN;
+    rc = check_probe_ptrs(code, code_flip, lin, lin_w, lin_b, lin_out, desc->lin_kind == STEGO_PROBE_ARGMAX ? 8 : 4, clu, centroids, clu_out,
+                          desc->clu_kind == STEGO_PROBE_ARGMAX ? 8 : 4);
+    if (rc != STEGO_OK) return rc;
 
     const TilePlan pl = plan(desc);
     ProbeParams p{};
@@ -172,14 +168,5 @@ extern "C" int stego_probe_head(const StegoProbeDesc* desc, const StegoMap* code
     p.NPS = pl.NPS;
     const dim3 grid((unsigned)((desc->W + pl.TX - 1) / pl.TX), (unsigned)((desc->H + pl.TY - 1) / pl.TY), (unsigned)desc->B);
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    (void)hipGetLastError();
-    if (pl.NMAX == 8)
-        probe_head_kernel<8><<<grid, TPB, pl.lds, s>>>(p);
-    else if (pl.NMAX == 16)
-        probe_head_kernel<16><<<grid, TPB, pl.lds, s>>>(p);
-    else if (pl.NMAX == 32)
-        probe_head_kernel<32><<<grid, TPB, pl.lds, s>>>(p);
-    else
-        probe_head_kernel<64><<<grid, TPB, pl.lds, s>>>(p);
-    return hip_rc(hipGetLastError());
+    return hip_rc(stego::with_const<8, 16, 32, 64>(pl.NMAX, [&](auto N) { return stego::launch_first<probe_head_kernel<N()>>(grid, TPB, pl.lds, s, p); }));
 }

@@ -645,32 +645,14 @@ Plan plan(const StegoProbeTrainDesc* d)
     const size_t clu_floats = d->n_clu ? (size_t)CP * (pl.KS + pl.NPS) + pl.NMAX : 0;
     pl.lds = ((size_t)RED_FLOATS + std::max(lin_floats, clu_floats)) * 4;
     pl.lds = (pl.lds + 15) & ~(size_t)15;
-    size_t o = 0;
-    pl.off_cnt = o;
-    o += (size_t)pl.g_lin * 8;
-    pl.off_part_lin = o;
-    o += (size_t)pl.g_lin * d->n_lin * (d->K + 1) * 4;
-    pl.off_loss_lin = o;
-    o += (size_t)pl.g_lin * 4;
-    pl.off_part_clu = o;
-    o += (size_t)pl.g_clu * d->n_clu * d->K * 4;
-    pl.off_loss_clu = o;
-    o += (size_t)pl.g_clu * 4;
-    pl.ws_bytes = (o + 7) & ~(size_t)7;
+    stego::WsLayout ws;                          // packed tight: the 8-byte counts come first, everything after them is 4-byte data
+    pl.off_cnt = ws.take((size_t)pl.g_lin * 8, 1);
+    pl.off_part_lin = ws.take((size_t)pl.g_lin * d->n_lin * (d->K + 1) * 4, 1);
+    pl.off_loss_lin = ws.take((size_t)pl.g_lin * 4, 1);
+    pl.off_part_clu = ws.take((size_t)pl.g_clu * d->n_clu * d->K * 4, 1);
+    pl.off_loss_clu = ws.take((size_t)pl.g_clu * 4, 1);
+    pl.ws_bytes = ws.total(8);
     return pl;
-}
-
-template <int NMAX>
-hipError_t launch_main(const TrainParams& p, unsigned grid, size_t lds, hipStream_t s)
-{
-    constexpr auto kernel = &probe_train_kernel<NMAX>;       // (named once: the attribute and the launch mean the same instantiation)
-    if (lds > 64 * 1024) {                       // beyond the default limit of dynamic LDS
-        const hipError_t e = stego::allow_dynamic_lds<kernel>((int)lds);
-        if (e != hipSuccess) return e;
-    }
-    (void)hipGetLastError();
-    kernel<<<grid, TPB, lds, s>>>(p);
-    return hipGetLastError();
 }
 
 }  // namespace
@@ -704,18 +686,18 @@ extern "C" int stego_probe_train(const StegoProbeTrainDesc* desc, const StegoMap
         return STEGO_ERR_ALIGN;
     if (clu && (!aligned(clusters, 4) || !aligned(d_clusters, 4))) return STEGO_ERR_ALIGN;
 
-    char* ws = static_cast<char*>(workspace);
+    using stego::at;
     TrainParams p{};
     p.code = *code;
     p.label = label;
     p.lin_w = lin_w;
     p.lin_b = lin_b;
     p.clusters = clusters;
-    p.cnt_lin = reinterpret_cast<long long*>(ws + pl.off_cnt);
-    p.part_lin = reinterpret_cast<float*>(ws + pl.off_part_lin);
-    p.loss_lin = reinterpret_cast<float*>(ws + pl.off_loss_lin);
-    p.part_clu = reinterpret_cast<float*>(ws + pl.off_part_clu);
-    p.loss_clu = reinterpret_cast<float*>(ws + pl.off_loss_clu);
+    p.cnt_lin = at<long long>(workspace, pl.off_cnt);
+    p.part_lin = at<float>(workspace, pl.off_part_lin);
+    p.loss_lin = at<float>(workspace, pl.off_loss_lin);
+    p.part_clu = at<float>(workspace, pl.off_part_clu);
+    p.loss_clu = at<float>(workspace, pl.off_loss_clu);
     p.K = desc->K;
     p.h = desc->h;
     p.w = desc->w;
@@ -761,18 +743,9 @@ extern "C" int stego_probe_train(const StegoProbeTrainDesc* desc, const StegoMap
 
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const unsigned grid = (unsigned)(pl.g_lin + pl.g_clu);
-    hipError_t e;
-    if (pl.NMAX == 8)
-        e = launch_main<8>(p, grid, pl.lds, s);
-    else if (pl.NMAX == 16)
-        e = launch_main<16>(p, grid, pl.lds, s);
-    else if (pl.NMAX == 32)
-        e = launch_main<32>(p, grid, pl.lds, s);
-    else
-        e = launch_main<64>(p, grid, pl.lds, s);
+    const hipError_t e = stego::with_const<8, 16, 32, 64>(pl.NMAX, [&](auto N) { return stego::launch_first<probe_train_kernel<N()>>(grid, TPB, pl.lds, s, p); });
     if (e != hipSuccess) return hip_rc(e);
     // rows of the linear probe, its loss, rows of the cluster probe, its loss
     const unsigned rgrid = (unsigned)(desc->n_lin + (lin ? 1 : 0) + desc->n_clu + (clu ? 1 : 0));
-    probe_train_reduce<<<rgrid, TPB, 0, s>>>(r);
-    return hip_rc(hipGetLastError());
+    return hip_rc(stego::launch_next<probe_train_reduce>(rgrid, TPB, 0, s, r));
 }

@@ -21,6 +21,7 @@
 #include <cstdint>
 
 #include "../../include/stego_rec.h"
+#include "addon_device.h"
 #include "host_util.h"
 
 namespace {
@@ -40,9 +41,6 @@ struct RecParams {
     int32_t B, K, C, h, w, T, CP, n_tiles, n_wg, n_rg, wgrad;
     float inv_t;
 };
-
-// row of a 32 x 32 accumulator tile that register r of lane half hf holds (the C / D layout of the 32x32 matrix instructions)
-__device__ inline int acc_row(int r, int hf) { return (r & 3) + 8 * (r >> 2) + 4 * hf; }
 
 // A value the tile loop needs once per tile, moved to a vector register: the loop's scalar registers are for what its inner loops use.
 template <class V>
@@ -283,13 +281,8 @@ __global__ __launch_bounds__(FIN_TPB) void rec_finish(RecParams p, int elem_bloc
     if ((int)blockIdx.x >= elem_blocks) {               // the loss: the last block of the grid
         double s = 0.0;
         for (int i = t; i < p.n_tiles; i += FIN_TPB) s += p.tile_part[i];
-        red[t] = s;
-        __syncthreads();
-        for (int m = FIN_TPB / 2; m > 0; m >>= 1) {
-            if (t < m) red[t] += red[t + m];
-            __syncthreads();
-        }
-        if (t == 0) p.loss[0] = (float)(-red[0] / (double)p.T);
+        s = block_sum<FIN_TPB>(s, red);
+        if (t == 0) p.loss[0] = (float)(-s / (double)p.T);
         return;
     }
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63, li = lane & 31, hf = lane >> 5;
@@ -450,8 +443,6 @@ struct Plan {
     size_t off_slabs, off_part, off_scal, off_count, ws_bytes;
 };
 
-inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 Plan plan(const StegoRecDesc* d)
 {
     Plan pl{};
@@ -467,30 +458,13 @@ Plan plan(const StegoRecDesc* d)
     pl.wgs[0] = pl.n_wg;
     pl.lds[1] = (size_t)FIN_TPB * 8 + std::max((size_t)(WAVES - 1) * (pl.NT * 16 + 1) * 64, (size_t)WAVES * TILE * (32 * pl.NT + 1)) * 4 + 4;
     pl.wgs[1] = pl.elem_blocks + 1;
-    size_t o = 0;
-    pl.off_slabs = o;
-    o = up16(o + (size_t)pl.n_rg * slab_len * 4);
-    pl.off_part = o;
-    o = up16(o + (size_t)pl.n_tiles * 8);
-    pl.off_scal = o;
-    o = up16(o + (size_t)pl.T * 2 * 4);
-    pl.off_count = o;
-    o = up16(o + (size_t)(pl.CP / 32) * 4);
-    pl.ws_bytes = o;
+    stego::WsLayout ws;
+    pl.off_slabs = ws.take((size_t)pl.n_rg * slab_len * 4, 16);
+    pl.off_part = ws.take((size_t)pl.n_tiles * 8, 16);
+    pl.off_scal = ws.take((size_t)pl.T * 2 * 4, 16);
+    pl.off_count = ws.take((size_t)(pl.CP / 32) * 4, 16);
+    pl.ws_bytes = ws.total(16);
     return pl;
-}
-
-template <int NT>
-hipError_t launch_tiles_as(const RecParams& p, unsigned grid, size_t lds, hipStream_t s)
-{
-    constexpr auto kernel = &rec_tiles<NT>;             // (named once: the attribute and the launch mean the same instantiation)
-    if (lds > 64 * 1024) {                              // beyond the default limit of dynamic LDS
-        const hipError_t e = stego::allow_dynamic_lds<kernel>((int)lds);
-        if (e != hipSuccess) return e;
-    }
-    (void)hipGetLastError();
-    kernel<<<grid, TPB, lds, s>>>(p);
-    return hipGetLastError();
 }
 
 }  // namespace
@@ -505,11 +479,7 @@ extern "C" int stego_rec_loss_plan(const StegoRecDesc* desc, size_t lds_bytes[ST
     const int rc = check_desc(desc);
     Plan pl{};
     if (rc == STEGO_OK) pl = plan(desc);
-    for (int i = 0; i < STEGO_REC_LAUNCHES; ++i) {
-        if (lds_bytes) lds_bytes[i] = pl.lds[i];
-        if (workgroups) workgroups[i] = pl.wgs[i];
-    }
-    return rc;
+    return stego::report_plan(rc, STEGO_REC_LAUNCHES, pl.lds, pl.wgs, lds_bytes, workgroups);
 }
 
 extern "C" int stego_rec_loss(const StegoRecDesc* desc, const StegoMap* code, const StegoMap* feats, const float* weight, const float* bias,
@@ -526,15 +496,15 @@ extern "C" int stego_rec_loss(const StegoRecDesc* desc, const StegoMap* code, co
         (d_code && !aligned(d_code->data, 4)) || !aligned(d_weight, 4) || !aligned(d_bias, 4) || !aligned(workspace, 16))
         return STEGO_ERR_ALIGN;
 
-    char* ws = static_cast<char*>(workspace);
+    using stego::at;
     RecParams p{};
     p.code = *code;
     p.feats = *feats;
     if (d_code) p.dcode = *d_code;
     p.weight = weight;
     p.bias = bias;
-    p.slabs = reinterpret_cast<float*>(ws + pl.off_slabs);
-    p.tile_part = reinterpret_cast<double*>(ws + pl.off_part);
+    p.slabs = at<float>(workspace, pl.off_slabs);
+    p.tile_part = at<double>(workspace, pl.off_part);
     p.loss = loss;
     p.d_weight = d_weight;
     p.d_bias = d_bias;
@@ -548,20 +518,17 @@ extern "C" int stego_rec_loss(const StegoRecDesc* desc, const StegoMap* code, co
     p.n_tiles = pl.n_tiles;
     p.n_wg = pl.n_wg;
     p.n_rg = pl.n_rg;
-    p.gscal = reinterpret_cast<float*>(ws + pl.off_scal);
-    p.counters = reinterpret_cast<unsigned*>(ws + pl.off_count);
+    p.gscal = at<float>(workspace, pl.off_scal);
+    p.counters = at<unsigned>(workspace, pl.off_count);
     p.wgrad = (d_weight || d_bias) ? 1 : 0;
     p.inv_t = (float)(1.0 / (double)pl.T);
 
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    const hipError_t e = stego::with_const<1, 2, 3, 4>(pl.NT, [&](auto N) { return launch_tiles_as<N()>(p, (unsigned)p.n_wg, pl.lds[0], s); });
+    const hipError_t e = stego::with_const<1, 2, 3, 4>(pl.NT, [&](auto N) { return stego::launch_first<rec_tiles<N()>>((unsigned)p.n_wg, TPB, pl.lds[0], s, p); });
     if (e != hipSuccess) return hip_rc(e);
     // the (range, chunk) workgroups of d_weight / d_bias (none without them), and one more block for the loss
     const int elem_blocks = p.wgrad ? pl.elem_blocks : 0;
-    const hipError_t e2 = stego::with_const<1, 2, 3, 4>(pl.NT, [&](auto N) {
-        (void)hipGetLastError();
-        rec_finish<N()><<<(unsigned)elem_blocks + 1, FIN_TPB, 0, s>>>(p, elem_blocks);
-        return hipGetLastError();
-    });
-    return hip_rc(e2);
+    return hip_rc(stego::with_const<1, 2, 3, 4>(pl.NT, [&](auto N) {
+        return stego::launch_first<rec_finish<N()>>((unsigned)elem_blocks + 1, FIN_TPB, 0, s, p, elem_blocks);
+    }));
 }

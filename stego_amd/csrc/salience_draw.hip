@@ -185,10 +185,7 @@ extern "C" int stego_salience_coords(const StegoSalienceDesc* desc, const void* 
         return STEGO_ERR_ALIGN;
     SalParams p{{mask1, mask2}, u, u_mix, {reg1, reg2}, {coords1, coords2}, desc->B, desc->H, desc->W, desc->S * desc->S};
     const dim3 grid((unsigned)desc->B, 2u);
-    (void)hipGetLastError();
-    if (f32)
-        salience_draw_kernel<true><<<grid, TPB, 0, static_cast<hipStream_t>(stream)>>>(p);
-    else
-        salience_draw_kernel<false><<<grid, TPB, 0, static_cast<hipStream_t>(stream)>>>(p);
-    return hip_rc(hipGetLastError());
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    if (f32) return hip_rc(stego::launch_first<salience_draw_kernel<true>>(grid, TPB, 0, s, p));
+    return hip_rc(stego::launch_first<salience_draw_kernel<false>>(grid, TPB, 0, s, p));
 }

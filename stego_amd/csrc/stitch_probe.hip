@@ -364,12 +364,9 @@ extern "C" int stego_stitch_probe(const StegoStitchDesc* desc, const StegoMap* c
     const int ny = axis_windows(l.H, l.win, l.stride), nx = axis_windows(l.W, l.win, l.stride);
     if ((int64_t)desc->T != (int64_t)ny * nx) return STEGO_ERR_STITCH_WINDOWS;
     const bool lin = desc->lin_kind != STEGO_PROBE_SKIP, clu = desc->clu_kind != STEGO_PROBE_SKIP;
-    if (!code || !code->data || (code_flip && !code_flip->data)) return STEGO_ERR_NULL;
-    if ((lin && (!lin_w || !lin_b || !lin_out)) || (clu && (!centroids || !clu_out))) return STEGO_ERR_NULL;
-    if (!aligned(code->data, 4) || (code_flip && !aligned(code_flip->data, 4))) return STEGO_ERR_ALIGN;
-    if (lin && (!aligned(lin_w, 4) || !aligned(lin_b, 4) || !aligned(lin_out, desc->lin_kind == STEGO_PROBE_ARGMAX ? 8 : 4)))
-        return STEGO_ERR_ALIGN;
-    if (clu && (!aligned(centroids, 4) || !aligned(clu_out, desc->clu_kind == STEGO_PROBE_ARGMAX ? 8 : 4))) return STEGO_ERR_ALIGN;
+    rc = check_probe_ptrs(code, code_flip, lin, lin_w, lin_b, lin_out, desc->lin_kind == STEGO_PROBE_ARGMAX ? 8 : 4, clu, centroids, clu_out,
+                          desc->clu_kind == STEGO_PROBE_ARGMAX ? 8 : 4);
+    if (rc != STEGO_OK) return rc;
 
     const TilePlan pl = plan(desc);
     if (pl.lds > LDS_BUDGET) return STEGO_ERR_UNSUPPORTED;          // (a 1 x 1 tile always fits: 4 footprint pixels at the most)
@@ -410,25 +407,22 @@ extern "C" int stego_stitch_probe(const StegoStitchDesc* desc, const StegoMap* c
     p.NPS = pl.NPS;
     const dim3 grid((unsigned)((l.W + pl.TX - 1) / pl.TX), (unsigned)((l.H + pl.TY - 1) / pl.TY));
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    (void)hipGetLastError();
-    if (pl.NMAX == 8)
-        stitch_probe_kernel<8, true, true, PASS_ALL><<<grid, TPB, pl.lds, s>>>(p);
-    else if (pl.NMAX == 16)
-        stitch_probe_kernel<16, true, true, PASS_ALL><<<grid, TPB, pl.lds, s>>>(p);
-    else if (pl.NMAX == 32)
-        stitch_probe_kernel<32, true, true, PASS_ALL><<<grid, TPB, pl.lds, s>>>(p);
-    else {
-        const dim3 sole_grid(grid.x, grid.y, SOLE_SLOTS * SOLE_SLOTS);
-        if (lin) {
-            stitch_probe_kernel<64, true, false, PASS_SOLE><<<sole_grid, TPB, pl.lds, s>>>(p);
-            stitch_probe_kernel<64, true, false, PASS_BLEND><<<grid, TPB, pl.lds, s>>>(p);
-        }
-        if (clu) {
-            stitch_probe_kernel<64, false, true, PASS_SOLE><<<sole_grid, TPB, pl.lds, s>>>(p);
-            stitch_probe_kernel<64, false, true, PASS_BLEND><<<grid, TPB, pl.lds, s>>>(p);
-        }
+    if (pl.NMAX < 64)                                   // (label_slots: 8, 16 or 32)
+        return hip_rc(stego::with_const<8, 16, 32>(pl.NMAX, [&](auto N) {
+            return stego::launch_first<stitch_probe_kernel<N(), true, true, PASS_ALL>>(grid, TPB, pl.lds, s, p);
+        }));
+    // 64 label slots: a probe at a time, the pixels one window covers first, then the blended ones
+    const dim3 sole_grid(grid.x, grid.y, SOLE_SLOTS * SOLE_SLOTS);
+    hipError_t e = hipSuccess;
+    if (lin) {
+        e = stego::launch_first<stitch_probe_kernel<64, true, false, PASS_SOLE>>(sole_grid, TPB, pl.lds, s, p);
+        if (e == hipSuccess) e = stego::launch_next<stitch_probe_kernel<64, true, false, PASS_BLEND>>(grid, TPB, pl.lds, s, p);
     }
-    return hip_rc(hipGetLastError());
+    if (clu && e == hipSuccess) {
+        e = stego::launch_first<stitch_probe_kernel<64, false, true, PASS_SOLE>>(sole_grid, TPB, pl.lds, s, p);
+        if (e == hipSuccess) e = stego::launch_next<stitch_probe_kernel<64, false, true, PASS_BLEND>>(grid, TPB, pl.lds, s, p);
+    }
+    return hip_rc(e);
 }
 
 extern "C" int stego_window_gather(const StegoWindowLayout* layout, const StegoMap* img, int32_t t0, int32_t n, float* out,
@@ -452,7 +446,5 @@ extern "C" int stego_window_gather(const StegoWindowLayout* layout, const StegoM
     p.nx = nx;
     p.t0 = t0;
     const dim3 grid((unsigned)((layout->win * layout->win + TPB - 1) / TPB), 3u, (unsigned)n);
-    (void)hipGetLastError();
-    window_gather_kernel<<<grid, TPB, 0, static_cast<hipStream_t>(stream)>>>(p);
-    return hip_rc(hipGetLastError());
+    return hip_rc(stego::launch_first<window_gather_kernel>(grid, TPB, 0, static_cast<hipStream_t>(stream), p));
 }
