@@ -7,7 +7,7 @@
 //      dA  = (dAn - An <An,dAn>) / ||a||             (F.normalize backward), likewise dB
 // Output: per (tile, side) the gradient w.r.t. the RAW sampled codes, DT[tile][side][128][LDK].
 //   bwd_tile_body<NT>           GEMMs on v_mfma_f32_16x16x4_f32 (exact fp32), 256 threads, K <= 80
-//   bwd_tile_h_body<NT, DENSE>  GEMMs as split-fp16 products on v_mfma_f32_16x16x16_f16, 512 threads, K <= 128
+//   bwd_tile_h_body<NT, DENSE>  GEMMs as split-fp16 products on v_mfma_f32_16x16x32_f16, 512 threads, K <= 128
 // LDS carve, workgroup sizes and debug bits: corr_bwd_plan.h.
 #pragma once
 #include "corr_bwd_plan.h"
@@ -225,19 +225,18 @@ __device__ __forceinline__ void bwd_tile_body(const BwdParams& prm, const int ti
 // ------------------------------------------------------------------------------- tile kernel, split-fp16 GEMMs
 // The same backward with the two code GEMMs on the fp16 matrix cores (forward() semantics: precision F16X3, and any mode once
 // K > 80; the fp32 MFMA of the kernel above runs at the VALU rate on gfx950: 2 x 4.3 us per tile).  Every fp32 operand is
-// split into fp16 hi + lo and a product is hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x16_f16 with fp32 accumulation, as in
-// the forward.  MFMA operands must be k-contiguous per lane:
+// split into fp16 hi + lo and a product is hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_f16 with fp32 accumulation, as in
+// the forward (the K = 32 form takes the time of the K = 16 form on gfx950: half the issues).  MFMA operands must be k-contiguous
+// per lane, 8 halves each:
 //   CT [side][hi|lo][channel][point]   the normalised sampled codes of both sides, TRANSPOSED on the way into LDS
 //   Gh/Gl [row][col]                   G, row-major, times one power of two per tile
-//   dAn^T = Bn^T . G^T    A operand = rows of CT(B), B operand = rows of G (k = column: 8-byte reads)
-//   dBn^T = An^T . G      A operand = rows of CT(A) (k = anchor point), B operand = COLUMNS of G, gathered as 4 x 2 bytes
-//                         per lane and step (a transposed copy of G does not fit next to CT: 157 KB are in use)
+//   dAn^T = Bn^T . G^T    A operand = rows of CT(B), B operand = rows of G (k = column: 16-byte reads)
+//   dBn^T = An^T . G      A operand = rows of CT(A) (k = anchor point), B operand = COLUMNS of G, gathered by two transposing
+//                         8-byte reads per lane and step (a transposed copy of G does not fit next to CT: 157 KB are in use)
 // Scale: G's entries are ~1e-7 (upstream 1 / (B P^2)).  One power of two per tile brings the largest |g| (scalar upstreams: the
 // bound 4 |gl|; tensor upstreams, DENSE: the exact maximum, one wave reduction + 8 partials through LDS) into [0.5, 1); fp16
 // hi + lo then resolve 2^-25 of that absolutely - fp32 accuracy relative to the largest entries, which is what a 128-term sum needs.
 // Channel tiles beyond 5 (K > 80) are processed in two groups that share the G image.
-
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 // normalize-backward of the B side's gradient held TRANSPOSED in MFMA 16x16 C/D layout and store to DT:
 // d[mc][np][reg] <-> channel 16 mc + 4 (lane >> 4) + reg, point 16 (NP wave + np) + (lane & 15).
@@ -464,8 +463,25 @@ __device__ __forceinline__ void bwd_tile_h_body(const BwdParams& prm, const int 
         *reinterpret_cast<unsigned*>(Gl + r * HB_LDR + 2 * lane) = lo;
     }
 
-    // lane map of v_mfma_f32_16x16x16_f16: A[i = lane & 15][k = 4 (lane >> 4) + 0..3], B[k = 4 (lane >> 4) + 0..3][j = lane & 15]
+    // lane map of v_mfma_f32_16x16x32_f16: A[i = lane & 15][k = 8 (lane >> 4) + 0..7], B[k = 8 (lane >> 4) + 0..7][j = lane & 15];
+    // C/D as the K = 16 form's (column lane & 15, row 4 (lane >> 4) + reg): half the issues of that form for the same sum
     const int cl = lane & 15, kq = lane >> 4;
+    // a lane's 8 points kk + 8 kq .. + 7 of channel row `row` (channel tile mc) of a code image: the 4-point groups 2 j and 2 j + 1,
+    // j = kk / 8 + kq.  convert_codes put group g at g ^ mc, so the two sit at (2 j) ^ mc and ((2 j) ^ mc) ^ 1: ONE aligned 16-byte
+    // block, (j ^ (mc >> 1)), with its 8-byte halves exchanged when mc is odd.  That exchange is a permutation of k inside the lane:
+    // the product only needs both operands to run through k alike, so an odd tile is multiplied with a G fragment whose halves are
+    // exchanged too (gemm_dB: the two transposed reads joined the other way round; gemm_dA: the 16 bytes of the row, halves exchanged) -
+    // one extra copy of the G fragments per k step where exchanging the code fragments would take one per odd tile.
+    // (Rows 272 B apart: the 16 lanes of a read hit 16 distinct 4-dword bank groups.)
+    auto ct_frag = [&](const half_t* row, int kk, int mc) {
+        return *reinterpret_cast<const f16x8*>(row + ((((kk >> 3) + kq) ^ (mc >> 1)) << 3));
+    };
+    auto join = [](const void* first, const void* second) {
+        f16x8 v;
+        __builtin_memcpy(&v, first, 8);
+        __builtin_memcpy(reinterpret_cast<char*>(&v) + 8, second, 8);
+        return v;
+    };
     half_t* ATh = CT;                                 // side 0 = anchors
     half_t* ATl = CT + CTR * HB_LDR;
     half_t* BTh = sameAB ? ATh : CT + 2 * CTR * HB_LDR;
@@ -494,21 +510,26 @@ __device__ __forceinline__ void bwd_tile_h_body(const BwdParams& prm, const int 
             // ---- dAn^T = Bn^T . G^T: channel rows of CT(B) (A operand) against the ROWS 16 (HW_NP wave + np) + j of G (B operand:
             // B[k][j] = G[j][k], k-contiguous in a row-major G)
             {
-                const int ra = cl * HB_LDR + 4 * kq;
-                const int rg = (16 * HW_NP * wave + cl) * HB_LDR + 4 * kq;
+                const int ra = cl * HB_LDR;
+                const int rg = (16 * HW_NP * wave + cl) * HB_LDR + 8 * kq;          // 8 contiguous halves of a row of G: one 16-byte read
 #pragma unroll 2
-                for (int kk = 0; kk < TP; kk += 16) {
-                    f16x4 ah[NTG], al[NTG], bh[HW_NP], bl[HW_NP];
+                for (int kk = 0; kk < TP; kk += 32) {
+                    f16x8 ah[NTG], al[NTG], bh[HW_NP][2], bl[HW_NP][2];           // b.[np][1]: halves exchanged, for the odd channel tiles
 #pragma unroll
                     for (int mc = 0; mc < NTG; ++mc) {
-                        const int ks = ((((kk >> 2) + kq) ^ mc) << 2) - 4 * kq;          // swizzled 4-point group (see convert_codes)
-                        ah[mc] = *reinterpret_cast<const f16x4*>(BTh + ra + 16 * mc * HB_LDR + ks);
-                        al[mc] = *reinterpret_cast<const f16x4*>(BTl + ra + 16 * mc * HB_LDR + ks);
+                        ah[mc] = ct_frag(BTh + ra + 16 * mc * HB_LDR, kk, mc);
+                        al[mc] = ct_frag(BTl + ra + 16 * mc * HB_LDR, kk, mc);
                     }
 #pragma unroll
                     for (int np = 0; np < HW_NP; ++np) {
-                        bh[np] = *reinterpret_cast<const f16x4*>(Gh + rg + 16 * np * HB_LDR + kk);
-                        bl[np] = *reinterpret_cast<const f16x4*>(Gl + rg + 16 * np * HB_LDR + kk);
+                        const half_t* gh = Gh + rg + 16 * np * HB_LDR + kk;
+                        const half_t* gl = Gl + rg + 16 * np * HB_LDR + kk;
+                        bh[np][0] = *reinterpret_cast<const f16x8*>(gh);
+                        bl[np][0] = *reinterpret_cast<const f16x8*>(gl);
+                        if (NTG > 1) {
+                            bh[np][1] = join(gh + 4, gh);
+                            bl[np][1] = join(gl + 4, gl);
+                        }
                     }
                     // the three terms outermost: consecutive MFMAs never wait for each other's accumulator
 #pragma unroll
@@ -518,37 +539,41 @@ __device__ __forceinline__ void bwd_tile_h_body(const BwdParams& prm, const int 
 #pragma unroll
                             for (int np = 0; np < HW_NP; ++np)
                                 if (grp * NTG + mc < NT)
-                                    dAt[grp * NTG + mc][np] = __builtin_amdgcn_mfma_f32_16x16x16f16(
-                                        term == 2 ? al[mc] : ah[mc], term == 1 ? bl[np] : bh[np], dAt[grp * NTG + mc][np], 0, 0, 0);
+                                    dAt[grp * NTG + mc][np] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                                        term == 2 ? al[mc] : ah[mc], term == 1 ? bl[np][mc & 1] : bh[np][mc & 1], dAt[grp * NTG + mc][np], 0, 0, 0);
                 }
             }
         };
         auto gemm_dB = [&]() {
             // ---- dBn^T = An^T . G: channel rows of CT(A) against the COLUMNS 16 (HW_NP wave + np) + j of G (k = anchor point),
-            // gathered as 4 x 2 bytes per lane and step
+            // gathered by the transposing LDS read
             {
-                const int ra = cl * HB_LDR + 4 * kq;                          // CT(A): channel cl (+16 mc), k = kk + 4 kq ..
-                // G: row kk + 4 kq + e, column 16 (HW_NP wave + np) + cl - four ROWS of one column per lane: the LDS transposes
+                const int ra = cl * HB_LDR;                                   // CT(A): channel cl (+16 mc), k = kk + 8 kq ..
+                // G: row kk + 8 kq + e, column 16 (HW_NP wave + np) + cl - eight ROWS of one column per lane: the LDS transposes
                 // (ds_read_b64_tr_b16: lane p of a 16-lane group passes the address of row p >> 2, columns 4 (p & 3) .. + 3 of a
-                // [4 rows][16 columns] block and receives column p, rows 0..3; one read per fragment instead of four 2-byte reads)
-                const int gt = (4 * kq + (cl >> 2)) * HB_LDR + 16 * HW_NP * wave + 4 * (cl & 3);
+                // [4 rows][16 columns] block and receives column p, rows 0..3; two reads per fragment - rows + 0..3 and + 4..7 -
+                // instead of eight 2-byte reads)
+                const int gt = (8 * kq + (cl >> 2)) * HB_LDR + 16 * HW_NP * wave + 4 * (cl & 3);
                 typedef __fp16 fp16x4v __attribute__((__vector_size__(4 * sizeof(__fp16))));
                 typedef __attribute__((address_space(3))) fp16x4v* lds_tr_ptr;
 #pragma unroll 2
-                for (int kk = 0; kk < TP; kk += 16) {
-                    f16x4 ah[NTG], al[NTG], bh[HW_NP], bl[HW_NP];
+                for (int kk = 0; kk < TP; kk += 32) {
+                    f16x8 ah[NTG], al[NTG], bh[HW_NP][2], bl[HW_NP][2];
 #pragma unroll
                     for (int mc = 0; mc < NTG; ++mc) {
-                        const int ks = ((((kk >> 2) + kq) ^ mc) << 2) - 4 * kq;
-                        ah[mc] = *reinterpret_cast<const f16x4*>(ATh + ra + 16 * mc * HB_LDR + ks);
-                        al[mc] = *reinterpret_cast<const f16x4*>(ATl + ra + 16 * mc * HB_LDR + ks);
+                        ah[mc] = ct_frag(ATh + ra + 16 * mc * HB_LDR, kk, mc);
+                        al[mc] = ct_frag(ATl + ra + 16 * mc * HB_LDR, kk, mc);
                     }
 #pragma unroll
                     for (int np = 0; np < HW_NP; ++np) {
-                        const fp16x4v th = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_tr_ptr)(Gh + gt + kk * HB_LDR + 16 * np));
-                        const fp16x4v tl = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_tr_ptr)(Gl + gt + kk * HB_LDR + 16 * np));
-                        __builtin_memcpy(&bh[np], &th, 8);
-                        __builtin_memcpy(&bl[np], &tl, 8);
+                        const fp16x4v th0 = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_tr_ptr)(Gh + gt + kk * HB_LDR + 16 * np));
+                        const fp16x4v th1 = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_tr_ptr)(Gh + gt + (kk + 4) * HB_LDR + 16 * np));
+                        const fp16x4v tl0 = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_tr_ptr)(Gl + gt + kk * HB_LDR + 16 * np));
+                        const fp16x4v tl1 = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_tr_ptr)(Gl + gt + (kk + 4) * HB_LDR + 16 * np));
+                        bh[np][0] = join(&th0, &th1);
+                        bl[np][0] = join(&tl0, &tl1);
+                        bh[np][1] = join(&th1, &th0);
+                        bl[np][1] = join(&tl1, &tl0);
                     }
 #pragma unroll
                     for (int term = 0; term < 3; ++term)
@@ -557,8 +582,8 @@ __device__ __forceinline__ void bwd_tile_h_body(const BwdParams& prm, const int 
 #pragma unroll
                             for (int np = 0; np < HW_NP; ++np)
                                 if (grp * NTG + mc < NT)
-                                    dBt[grp * NTG + mc][np] = __builtin_amdgcn_mfma_f32_16x16x16f16(
-                                        term == 2 ? al[mc] : ah[mc], term == 1 ? bl[np] : bh[np], dBt[grp * NTG + mc][np], 0, 0, 0);
+                                    dBt[grp * NTG + mc][np] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                                        term == 2 ? al[mc] : ah[mc], term == 1 ? bl[np][mc & 1] : bh[np][mc & 1], dBt[grp * NTG + mc][np], 0, 0, 0);
                 }
             }
         };
