@@ -214,6 +214,19 @@ REC_ERR_DIM, REC_ERR_SIZE = 140, 141
 REC_MAX_K, REC_MAX_C, REC_MAX_B, REC_MAX_SIDE, REC_MAX_TOKENS = 128, 1024, 65535, 2048, 1 << 24
 REC_TILE, REC_MAX_WORKGROUPS, REC_LAUNCHES = 32, 64, 2
 
+class StegoRenderDesc(Structure):
+    """include/stego_render.h"""
+    _fields_ = [(n, c_int32) for n in ("B", "H", "W", "n_lut", "label_dtype", "flags")] + \
+        [("alpha", c_float), ("mean", c_float * 3), ("std", c_float * 3), ("ignore_rgb", ctypes.c_uint8 * 4), ("edge_rgb", ctypes.c_uint8 * 4)] + \
+        [(n, c_int64) for n in ("label_stride_n", "label_stride_h", "label_stride_w", "out_stride_n", "out_stride_h")]
+
+
+RENDER_ERR_SIZE, RENDER_ERR_LUT, RENDER_ERR_DTYPE, RENDER_ERR_FLAGS, RENDER_ERR_PARAM, RENDER_ERR_SELECT = 150, 151, 152, 153, 154, 155
+RENDER_IMAGE, RENDER_LABELS, RENDER_EDGES, RENDER_BLEND, RENDER_RESCALE = 1, 2, 4, 8, 16
+RENDER_I64, RENDER_I32, RENDER_U8 = 0, 1, 2
+RENDER_DTYPES = {torch.int64: RENDER_I64, torch.int32: RENDER_I32, torch.uint8: RENDER_U8}
+RENDER_MAX_LUT, RENDER_MAX_B = 512, 65535
+
 # name -> (restype, argtypes); every symbol include/stego_corr.h declares
 _P = c_void_p
 _H = POINTER(StegoHeadDesc)
@@ -243,6 +256,9 @@ SIGNATURES = {
     "stego_stitch_probe": (c_int32, [POINTER(StegoStitchDesc), _M, _M] + [_P] * 5 + [_P]),
     "stego_stitch_probe_plan": (c_size_t, [POINTER(StegoStitchDesc)] + [POINTER(c_int32)] * 4),
     "stego_window_gather": (c_int32, [POINTER(StegoWindowLayout), _M, c_int32, c_int32, _P, _P, _P]),
+    "stego_image_range_workspace_bytes": (c_size_t, [POINTER(StegoRenderDesc)]),
+    "stego_image_range": (c_int32, [POINTER(StegoRenderDesc), _M, _P, _P, c_size_t, _P]),
+    "stego_render": (c_int32, [POINTER(StegoRenderDesc), _M, _P, _P, _P, _P, _P]),
     "stego_probe_confusion": (c_int32, [POINTER(StegoProbeConfusionDesc), _M, _M] + [_P] * 6 + [_P]),
     "stego_probe_confusion_plan": (c_size_t, [POINTER(StegoProbeConfusionDesc), POINTER(c_int32), POINTER(c_int32)]),
     "stego_confusion": (c_int32, [POINTER(StegoConfusionDesc), _P, _P, _P, _P]),
@@ -1366,6 +1382,59 @@ def window_gather(img, win, stride, t0, n, flip=False):
     with _on_device(dev):
         _check(window_gather_raw(layout, _map(img.unsqueeze(0)), t0, n, out, out_flip, _stream()))
     return (out, out_flip) if flip else out
+
+
+# ---- coloured pictures (include/stego_render.h; stego_amd.render wraps them for label maps, images and contact sheets)
+def render_desc(B, H, W, n_lut=1, label_dtype=RENDER_I64, flags=RENDER_LABELS, alpha=0.0, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0),
+                ignore_rgb=(0, 0, 0), edge_rgb=(0, 0, 0), label_strides=(0, 0, 1), out_strides=(0, 0)):
+    d = StegoRenderDesc(int(B), int(H), int(W), int(n_lut), int(label_dtype), int(flags), float(alpha))
+    for c in range(3):
+        d.mean[c], d.std[c] = float(mean[c]), float(std[c])
+        d.ignore_rgb[c], d.edge_rgb[c] = int(ignore_rgb[c]), int(edge_rgb[c])
+    d.label_stride_n, d.label_stride_h, d.label_stride_w = (int(v) for v in label_strides)
+    d.out_stride_n, d.out_stride_h = (int(v) for v in out_strides)
+    return d
+
+
+def image_range_workspace_bytes(desc):
+    """stego_image_range_workspace_bytes (host only); 0 for an invalid descriptor."""
+    return int(load().stego_image_range_workspace_bytes(byref(desc)))
+
+
+def image_range_raw(desc, image, rng, workspace, workspace_bytes, stream=None):
+    """stego_image_range with every argument given: `image` is a StegoMap (or None), the rest raw addresses or tensors -> the return
+    code, unchecked."""
+    return int(load().stego_image_range(_desc_ref(desc), _ref(image), _addr(rng), _addr(workspace), int(workspace_bytes),
+                                        stream if stream is not None else None))
+
+
+def render_raw(desc, image, labels, lut, rng, out, stream=None):
+    """stego_render with every argument given: `image` is a StegoMap (or None), the rest raw addresses or tensors -> the return code,
+    unchecked."""
+    return int(load().stego_render(_desc_ref(desc), _ref(image), _addr(labels), _addr(lut), _addr(rng), _addr(out),
+                                   stream if stream is not None else None))
+
+
+def image_range(desc, image):
+    """stego_image_range of the float32 image [B, 3, H, W] (any strides) -> float32 [B, 2], (lo, hi) per image."""
+    _require_dev(image)
+    dev = image.device
+    need = image_range_workspace_bytes(desc)
+    if need == 0:
+        _check(image_range_raw(desc, None, None, None, 0))
+    ws = _empty_bytes(need, dev)
+    rng = torch.empty((desc.B, 2), dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        _check(image_range_raw(desc, _map(image), rng, ws, need, _stream()))
+    return rng
+
+
+def render(desc, image, labels, lut, rng, out):
+    """stego_render on torch's current stream: `out` is a uint8 tensor whose first element is the target's base (the descriptor holds
+    its strides)."""
+    _require_dev(image, labels, lut, rng, out)
+    with _on_device(out.device):
+        _check(render_raw(desc, _map(image) if image is not None else None, labels, lut, rng, out, _stream()))
 
 
 # ---- device-side confusion matrices (include/stego_confusion.h; stego_amd.metrics wraps them for the trainer and evaluate())

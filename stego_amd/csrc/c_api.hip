@@ -20,6 +20,7 @@
 #include "../../include/stego_stitch.h"
 #include "../../include/stego_salience.h"
 #include "../../include/stego_rec.h"
+#include "../../include/stego_render.h"
 #include "corr_wide.h"
 #include "launchers.h"
 
@@ -376,6 +377,12 @@ const char* stego_error_string(int code)
         case STEGO_ERR_SALIENCE_DTYPE: return "salience draws: mask_dtype is neither STEGO_SALIENCE_U8 nor STEGO_SALIENCE_F32";
         case STEGO_ERR_REC_DIM: return "rec loss: K outside [1, 128] or C outside [1, 1024] (include/stego_rec.h)";
         case STEGO_ERR_REC_SIZE: return "rec loss: B outside [1, 65535], h or w outside [1, 2048], or B * h * w > 2^24";
+        case STEGO_ERR_RENDER_SIZE: return "render: B outside [1, 65535], or H or W outside [1, 32768] (include/stego_render.h)";
+        case STEGO_ERR_RENDER_LUT: return "render: n_lut outside [1, 512]";
+        case STEGO_ERR_RENDER_DTYPE: return "render: label_dtype is none of STEGO_RENDER_I64, STEGO_RENDER_I32, STEGO_RENDER_U8";
+        case STEGO_ERR_RENDER_FLAGS: return "render: unknown flag bit";
+        case STEGO_ERR_RENDER_PARAM: return "render: alpha outside [0, 1], or a mean or std that is not finite";
+        case STEGO_ERR_RENDER_SELECT: return "render: neither image nor labels selected, BLEND without both (or both without BLEND), EDGES without labels, or RESCALE without the image";
         case STEGO_ERR_CRF_RANGE: return "dense CRF: a lattice coordinate would leave the packed key (image too large for its standard deviations)";
         default: return code >= STEGO_ERR_HIP ? "HIP runtime error (code - 1000 = hipError_t)" : "unknown error";
     }

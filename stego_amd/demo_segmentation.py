@@ -11,6 +11,12 @@ ending the run, the files are read in sorted order, and DataParallel (`use_ddp`)
 With `full_res=True` no file is cropped or shrunk: each goes through stego_amd.segment.segment_large at its own size, as overlapping
 res x res windows `window_stride` apart (default: half a window) stitched on the device (csrc/stitch_probe.hip), and its PNGs have the
 image's size.  A file whose shorter side is below `res` is first resized so that it equals `res`.
+
+With `save_color=True` every prediction is also written as a picture (stego_amd.render, csrc/render.hip), coloured on the device
+before it is copied to the host: `linear_color/` and `cluster_color/` are the label maps through the model's `label_cmap`, and
+`overlay/` is the image, at weight 1 - `overlay_alpha`, under the cluster colours with the segment boundaries drawn.  The clusters
+are coloured by class through the checkpoint's cluster -> class assignment when it stores one (`model.cluster_to_class`), else by
+their own index.  `linear/` and `cluster/` and the returned list are the same with and without it.
 """
 import os
 import sys
@@ -96,6 +102,25 @@ def my_app(cfg):
             Image.fromarray(pred.astype(np.uint8)).save(path)          # 2-D uint8: mode "L"
             written.append(path)
 
+    save_color = getattr(cfg, "save_color", False)
+    if save_color:
+        from .render import IMAGENET_MEAN, IMAGENET_STD, colorize
+        for sub in ("linear_color", "cluster_color", "overlay"):
+            os.makedirs(join(out, sub), exist_ok=True)
+        cmap, mapping = model.label_cmap, model.cluster_to_class
+        overlay_alpha = float(getattr(cfg, "overlay_alpha", 0.5))
+
+    def save_colors(names, imgs, linear, cluster):
+        """The three pictures of every image of a batch on the device: imgs [N, 3, H, W], label maps [N, H, W]."""
+        pictures = (("linear_color", colorize(linear, cmap)),
+                    ("cluster_color", colorize(cluster, cmap, mapping=mapping)),
+                    ("overlay", colorize(cluster, cmap, mapping=mapping, image=imgs, alpha=overlay_alpha, edges=True,
+                                         mean=IMAGENET_MEAN, std=IMAGENET_STD)))
+        for sub, rgb in pictures:
+            rgb = rgb.cpu().numpy()
+            for j, name in enumerate(names):
+                Image.fromarray(rgb[j]).save(join(out, sub, prediction_name(name)))         # [H, W, 3] uint8: mode "RGB"
+
     if getattr(cfg, "full_res", False):
         dataset = UnlabeledImageFolder(cfg.image_dir, full_image_transform(cfg.res))
         loader = torch.utils.data.DataLoader(dataset, 1, shuffle=False, num_workers=cfg.num_workers, collate_fn=first)
@@ -103,8 +128,11 @@ def my_app(cfg):
             if img is None:
                 skipped.append(name)
                 continue
-            linear, cluster = segment_large(model, img.to(dev), window=cfg.res, stride=getattr(cfg, "window_stride", None),
+            img = img.to(dev)
+            linear, cluster = segment_large(model, img, window=cfg.res, stride=getattr(cfg, "window_stride", None),
                                             batch=cfg.batch_size * 2, run_crf=run_crf)
+            if save_color:
+                save_colors([name], img.unsqueeze(0), linear.unsqueeze(0), cluster.unsqueeze(0))
             save(name, linear.cpu().numpy(), cluster.cpu().numpy())
         if skipped:
             print("skipped %d file(s) PIL cannot read: %s" % (len(skipped), ", ".join(skipped)))
@@ -116,7 +144,10 @@ def my_app(cfg):
         skipped.extend(bad)
         if imgs is None:
             continue
-        linear, cluster = segment(model, imgs.to(dev), run_crf=run_crf)
+        imgs = imgs.to(dev)
+        linear, cluster = segment(model, imgs, run_crf=run_crf)
+        if save_color:
+            save_colors(names, imgs, linear, cluster)
         linear, cluster = linear.cpu().numpy(), cluster.cpu().numpy()
         for j, name in enumerate(names):
             save(name, linear[j], cluster[j])

@@ -1,8 +1,14 @@
-"""The reference's evaluation loop (``src/eval_segmentation.py:118-161``) without figures, PiCIE or DataParallel: flip-averaged code,
-both probes, the dense CRF (stego_amd.crf, on the device) and the final metrics.
+"""The reference's evaluation loop (``src/eval_segmentation.py:118-161``) without PiCIE or DataParallel: flip-averaged code, both
+probes, the dense CRF (stego_amd.crf, on the device) and the final metrics.
 
     python -m stego_amd.eval_segmentation model_paths=[run.ckpt] run_crf=True       # a CroppedDataset val split, or synthetic data
+
+With `save_figures=True` the qualitative figure of the reference (eval_segmentation.py:178-210) is written too, without matplotlib:
+the images `figure_images` names stay on the device with their labels and predictions, are coloured there (stego_amd.render) and
+saved as {img/N.jpg, label/N.png, linear/N.png, cluster/N.png} and as figure_K.png contact sheets of up to 10 columns with the rows
+image / label / linear probe / cluster probe, the clusters coloured by their Hungarian class.
 """
+import os
 import sys
 from os.path import dirname, exists, join
 
@@ -49,13 +55,29 @@ def _native_update(model, img, code1, code2, label, run_crf):
     model.test_cluster_metrics.update_scores(dense_crf_batch(bgr, cluster_probs), label)
 
 
-def evaluate(model, loader, run_crf=True, device=None, fused_head=False, native_metrics=False):
+def _kept_preds(model, img, code1, code2, size, run_crf):
+    """The label maps of a batch that native_metrics scored without any: the fused head's argmax, after the CRF with run_crf."""
+    if run_crf:
+        return _fused_preds(model, img, code1, code2, size, True)
+    from .segment import probe_head
+    return probe_head(model, code1, code2, size, linear="argmax", cluster="argmax")
+
+
+def evaluate(model, loader, run_crf=True, device=None, fused_head=False, native_metrics=False, keep=None):
     """eval_segmentation.py:118-161 over `loader` (batches with "img" / "label", or (img, label, ...) tuples) -> the metrics dict of
     model.test_linear_metrics and model.test_cluster_metrics (reset first, then updated batch by batch, then computed).
     fused_head: the flip average, resize and both probes in one launch (stego_amd.segment.probe_head), which writes the CRF's
     probabilities directly (run_crf) or the log-probabilities the argmax takes, instead of the torch chain.
     native_metrics: the confusion matrices are counted on the device (stego_amd.metrics) and read once, in compute(); implies the
-    fused head.  The model's test metrics become DeviceUnsupervisedMetrics for it when they are not already."""
+    fused head.  The model's test metrics become DeviceUnsupervisedMetrics for it when they are not already.
+    keep: indices of images, counted through the loader, whose image, label and both predictions stay on the device: afterwards
+    model.saved_data = {"index": [...], "img": [n, 3, H, W], "label", "linear_preds", "cluster_preds": [n, h, w]} in the order the
+    loader met them (the reference's saved_data).  With native_metrics the batches that hold one additionally run the fused head with
+    the argmax output, since the metrics path has no label map; the metrics do not change."""
+    keeping = keep is not None
+    keep = set(int(k) for k in keep) if keeping else set()
+    saved = {"index": [], "img": [], "label": [], "linear_preds": [], "cluster_preds": []}
+    seen = 0
     device = device or next(model.parameters()).device
     model.eval()
     if native_metrics:
@@ -72,8 +94,12 @@ def evaluate(model, loader, run_crf=True, device=None, fused_head=False, native_
             img, label = img.to(device), label.to(device)
             _, code1 = model.net(img)
             _, code2 = model.net(img.flip(dims=[3]))
+            wanted = [j for j in range(img.shape[0]) if seen + j in keep]
+            first, seen = seen, seen + img.shape[0]
             if native_metrics:
                 _native_update(model, img, code1, code2, label, run_crf)
+                if wanted:
+                    _keep(saved, wanted, first, img, label, *_kept_preds(model, img, code1, code2, label.shape[-2:], run_crf))
                 continue
             if fused_head:
                 linear_preds, cluster_preds = _fused_preds(model, img, code1, code2, label.shape[-2:], run_crf)
@@ -90,7 +116,58 @@ def evaluate(model, loader, run_crf=True, device=None, fused_head=False, native_
                     cluster_preds = cluster_probs.argmax(1)
             model.test_linear_metrics.update(linear_preds, label)
             model.test_cluster_metrics.update(cluster_preds, label)
+            if wanted:
+                _keep(saved, wanted, first, img, label, linear_preds, cluster_preds)
+    if keeping:
+        model.saved_data = {k: (torch.stack(v) if k != "index" else v) for k, v in saved.items()} if saved["index"] else saved
     return {**model.test_linear_metrics.compute(), **model.test_cluster_metrics.compute()}
+
+
+def _keep(saved, wanted, first, img, label, linear_preds, cluster_preds):
+    size = label.shape[-2:]
+    for j in wanted:
+        saved["index"].append(first + j)
+        saved["img"].append(img[j])
+        saved["label"].append(label[j].reshape(size))
+        saved["linear_preds"].append(linear_preds[j].reshape(size))
+        saved["cluster_preds"].append(cluster_preds[j].reshape(size))
+
+
+def result_dir(cfg, i=0):
+    base = join(getattr(cfg, "output_root", "../"), "results", "predictions", str(getattr(cfg, "experiment_name", "eval")))
+    return base if i == 0 else "%s_%d" % (base, i)
+
+
+def save_figures(model, out, columns=10):
+    """model.saved_data (evaluate(keep=...)) and the computed test_cluster_metrics -> the pictures under `out`; returns the paths.
+    Everything is coloured on the device; a picture crosses to the host as the uint8 bytes PIL writes."""
+    from PIL import Image
+
+    from .render import colorize, comparison_sheet, image_u8
+    data = model.saved_data
+    n = len(data["index"])
+    written = []
+    if n == 0:
+        return written
+    for sub in ("img", "label", "linear", "cluster"):
+        os.makedirs(join(out, sub), exist_ok=True)
+    cmap, mapping = model.label_cmap, model.test_cluster_metrics.cluster_to_class()
+    panels = (("img", ".jpg", image_u8(data["img"])), ("label", ".png", colorize(data["label"], cmap)),
+              ("linear", ".png", colorize(data["linear_preds"], cmap)),
+              ("cluster", ".png", colorize(data["cluster_preds"], cmap, mapping=mapping)))
+    for sub, ext, rgb in panels:
+        rgb = rgb.cpu().numpy()
+        for i in range(n):
+            written.append(join(out, sub, str(i) + ext))
+            Image.fromarray(rgb[i]).save(written[-1])
+    for k, lo in enumerate(range(0, n, columns)):
+        cols = slice(lo, lo + columns)
+        sheet = comparison_sheet([{"image": data["img"][cols]}, {"labels": data["label"][cols], "cmap": cmap},
+                                  {"labels": data["linear_preds"][cols], "cmap": cmap},
+                                  {"labels": data["cluster_preds"][cols], "cmap": cmap, "mapping": mapping}])
+        written.append(join(out, "figure_%d.png" % k))
+        Image.fromarray(sheet.cpu().numpy()).save(written[-1])
+    return written
 
 
 def make_loader(cfg, model):
@@ -119,11 +196,16 @@ def my_app(cfg):
     """eval_segmentation.py:57-161: every checkpoint of cfg.model_paths evaluated on the val split; returns {path: metrics}."""
     results = {}
     dev = torch.device("cuda", 0)
-    for model_path in cfg.model_paths:
+    figures = getattr(cfg, "save_figures", False)
+    wanted = getattr(cfg, "figure_images", None)
+    keep = (list(wanted) if wanted is not None else list(range(8))) if figures else None
+    for i, model_path in enumerate(cfg.model_paths):
         model = LitUnsupervisedSegmenter.load_from_checkpoint(model_path)
         model.eval().to(dev)
         metrics = evaluate(model, make_loader(cfg, model), run_crf=cfg.run_crf, device=dev, fused_head=getattr(cfg, "fused_head", False),
-                           native_metrics=getattr(cfg, "native_metrics", False))
+                           native_metrics=getattr(cfg, "native_metrics", False), keep=keep)
+        if figures:
+            save_figures(model, result_dir(cfg, i))
         print("")
         print(model_path)
         print({k: float(v) for k, v in metrics.items()})

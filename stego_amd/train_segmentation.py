@@ -16,6 +16,7 @@ import sys
 import types
 from os.path import dirname, join
 
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -134,6 +135,23 @@ class LitUnsupervisedSegmenter(nn.Module):
         self._fused = None               # cfg.native_optim: the FusedAdam behind the three optimizers (stego_amd.optim)
         self._reducer = None
         self._augmenter = None
+        self._cluster_to_class = None
+
+    @property
+    def label_cmap(self):
+        """The colormap of the model's dataset as a numpy [n, 3] array, as the reference's attribute (train_segmentation.py:100-103)."""
+        from .render import label_cmap
+        return label_cmap(self.cfg.dataset_name)
+
+    @property
+    def cluster_to_class(self):
+        """The class of every cluster of cluster_probe, -1 for none (UnsupervisedMetrics.cluster_to_class()): of the last validation
+        or evaluation that computed a Hungarian assignment, else what the checkpoint stored, else None.  demo_segmentation colours
+        its cluster pictures with it."""
+        for m in (self.test_cluster_metrics, self.cluster_metrics):
+            if hasattr(m, "assignments"):
+                return m.cluster_to_class()
+        return self._cluster_to_class
 
     # ---- checkpoints in the layout Lightning writes for the reference (train_segmentation.py:106 save_hyperparameters,
     #      :487 ModelCheckpoint) and that eval_segmentation.py:67 / demo_segmentation.py:41 read back with
@@ -145,6 +163,8 @@ class LitUnsupervisedSegmenter(nn.Module):
               "state_dict": self.state_dict(), "hyper_parameters": {"n_classes": self.n_classes, "cfg": cfg}}
         if self._optims is not None:
             ck["optimizer_states"] = [o.state_dict() for o in self._optims]
+        if self.cluster_to_class is not None:
+            ck["cluster_to_class"] = [int(c) for c in self.cluster_to_class]
         return ck
 
     def save_checkpoint(self, path, epoch=0):
@@ -168,6 +188,8 @@ class LitUnsupervisedSegmenter(nn.Module):
             for o, sd in zip(model.optimizers(), ck["optimizer_states"]):
                 o.load_state_dict(sd)
         model.load_result = result
+        if ck.get("cluster_to_class") is not None:
+            model._cluster_to_class = np.asarray(ck["cluster_to_class"], dtype=np.int64)
         return model
 
     # ---- the slice of the LightningModule protocol the reference uses

@@ -66,6 +66,28 @@ class UnsupervisedMetrics:
             stats = buf.cpu()
         return self._scores(stats)
 
+    def cluster_to_class(self):
+        """The class of every cluster id as an int64 numpy vector [n_classes + extra_clusters], -1 for a cluster without one: what
+        map_clusters() indexes, and what stego_amd.render.colorize(mapping=...) composes into its colour table.  Needs compute() to
+        have run (it holds the Hungarian assignment); without compute_hungarian the clusters are the classes.
+        With extra_clusters > 0 this is the reference's vector (utils.py:235-242) as it builds it: the classes of the matched
+        clusters in cluster order, then a -1 inserted at position m + 1 for every unmatched cluster m in ascending order (appended
+        when m equals the vector's length) - one place behind where cluster m itself sits."""
+        if not self.compute_hungarian:
+            return np.arange(self.n_classes, dtype=np.int64)
+        if not hasattr(self, "assignments"):
+            raise RuntimeError("cluster_to_class: compute() has not run yet, there is no assignment")
+        vec = np.asarray(self.assignments[1], dtype=np.int64)
+        if self.extra_clusters == 0:
+            return vec
+        for m in sorted(set(range(self.n_classes + self.extra_clusters)) - set(int(r) for r in self.assignments[0])):
+            vec = np.append(vec, -1) if m == vec.shape[0] else np.insert(vec, m + 1, -1)
+        return vec
+
+    def map_clusters(self, clusters):
+        """Cluster ids (an integer tensor of any shape, on any device) -> class ids of the same shape (utils.py:231-243)."""
+        return torch.as_tensor(self.cluster_to_class(), device=clusters.device)[clusters.long()]
+
     def _scores(self, stats):
         """mIoU and accuracy of one (already cross-rank summed) host matrix."""
         from scipy.optimize import linear_sum_assignment
