@@ -195,6 +195,25 @@ class StegoAdamDesc(Structure):
         [("grad_elems", c_int64), ("state_elems", c_int64), ("groups", StegoAdamGroup * ADAM_MAX_GROUPS)]
 
 
+class StegoStatsDesc(Structure):
+    """include/stego_stats.h"""
+    _fields_ = [("n_tensors", c_int32), ("n_scalars", c_int32), ("with_hist", c_int32), ("ring_slots", c_int32), ("counts", c_int64 * 4)]
+
+
+STATS_PLAN_FIELDS = ("grid", "chunk", "record_bytes", "off_step", "off_with_hist", "off_n_tensors", "off_tensors", "tensor_stride",
+                     "t_n_finite", "t_n_nan", "t_n_out", "t_sum", "t_sum_sq", "t_min", "t_max", "off_scalars", "off_hist", "hist_stride",
+                     "ring_bytes", "state_bytes", "workspace_bytes")
+
+
+class StegoStatsPlan(Structure):
+    """include/stego_stats.h: the launch and the record layout (byte offsets)"""
+    _fields_ = [(name, c_int64) for name in STATS_PLAN_FIELDS]
+
+
+STATS_ERR_COUNT, STATS_ERR_RING, STATS_ERR_FLAGS = 160, 161, 162
+STATS_MAX_TENSORS, STATS_MAX_SCALARS, STATS_MAX_ELEMS, STATS_MAX_SLOTS, STATS_BUCKETS, STATS_LIMITS = 4, 16, 1 << 31, 65536, 1548, 1549
+
+
 class StegoSalienceDesc(Structure):
     """include/stego_salience.h"""
     _fields_ = [(n, c_int32) for n in ("B", "H", "W", "S", "mask_dtype")]
@@ -264,6 +283,9 @@ SIGNATURES = {
     "stego_confusion": (c_int32, [POINTER(StegoConfusionDesc), _P, _P, _P, _P]),
     "stego_adam_step": (c_int32, [POINTER(StegoAdamDesc), _P, _P, _P, _P, _P, _P, _P, _P]),
     "stego_adam_plan": (c_int32, [POINTER(StegoAdamDesc), _P, POINTER(c_int32), POINTER(c_int32), POINTER(c_int64)]),
+    "stego_step_stats": (c_int32, [POINTER(StegoStatsDesc), _P, _P, _P, _P, _P, _P]),
+    "stego_step_stats_plan": (c_int32, [POINTER(StegoStatsDesc), POINTER(StegoStatsPlan)]),
+    "stego_step_stats_edges": (c_int32, [_P, _P]),
     "stego_pr_accumulate": (c_int32, [POINTER(StegoPrDesc), _M, _M] + [_P] * 6 + [_P]),
     "stego_pr_plan": (c_size_t, [POINTER(StegoPrDesc), POINTER(c_int32), POINTER(c_int32)]),
     "stego_probe_train_workspace_bytes": (c_size_t, [POINTER(StegoProbeTrainDesc)]),
@@ -1581,6 +1603,63 @@ def adam_step(desc, segments_host, segments, grads, exp_avg, exp_avg_sq, steps, 
     _require_dev(segments, grads, exp_avg, exp_avg_sq, steps, ticket)
     with _on_device(grads.device):
         _check(adam_step_raw(desc, segments_host, segments, grads, exp_avg, exp_avg_sq, steps, ticket, _stream()))
+
+
+# ---- device-side step statistics (include/stego_stats.h; stego_amd.step_stats.StepStats wraps them for the trainer)
+def stats_desc(counts, n_scalars, with_hist, ring_slots, n_tensors=None):
+    d = StegoStatsDesc(len(counts) if n_tensors is None else int(n_tensors), int(n_scalars), int(with_hist), int(ring_slots))
+    for i, c in enumerate(list(counts)[:STATS_MAX_TENSORS]):
+        d.counts[i] = int(c)
+    return d
+
+
+def step_stats_plan(desc):
+    """stego_step_stats_plan (host only) -> (return code, {field: value}); the dict is empty when the code is not 0."""
+    plan = StegoStatsPlan()
+    rc = int(load().stego_step_stats_plan(_desc_ref(desc), byref(plan)))
+    return rc, ({name: int(getattr(plan, name)) for name in STATS_PLAN_FIELDS} if rc == 0 else {})
+
+
+def step_stats_edges():
+    """stego_step_stats_edges (host only) -> (limits float64 [1549], thresholds float32 [1549]) as numpy arrays."""
+    import numpy as np
+    limits, thr = np.empty(STATS_LIMITS, np.float64), np.empty(STATS_LIMITS, np.float32)
+    _check(load().stego_step_stats_edges(limits.ctypes.data, thr.ctypes.data))
+    return limits, thr
+
+
+def step_stats_raw(desc, tensors, scalars, ring, state, workspace, stream=None):
+    """stego_step_stats with every argument given: `tensors` / `scalars` lists of tensors or raw addresses (or None for a NULL array),
+    the rest raw addresses or tensors (tests: the error codes) -> the return code, unchecked."""
+    def table(xs):
+        if xs is None:
+            return None
+        arr = (c_void_p * max(len(xs), 1))()
+        for i, x in enumerate(xs):
+            arr[i] = _addr(x)
+        return arr
+    return int(load().stego_step_stats(_desc_ref(desc), table(tensors), table(scalars), _addr(ring), _addr(state), _addr(workspace),
+                                       stream if stream is not None else None))
+
+
+def pointer_table(n):
+    """A host array of n device addresses (stego_step_stats's `tensors` / `scalars`), to be filled in place."""
+    return (c_void_p * max(int(n), 1))()
+
+
+def step_stats_call(desc, tensor_table, scalar_table, addresses, device):
+    """stego_step_stats on torch's current stream from tables the caller keeps (stego_amd.step_stats.StepStats: once per training
+    step): `addresses` = (ring, state, workspace) as integers."""
+    with _on_device(device):
+        _check(load().stego_step_stats(byref(desc), tensor_table, scalar_table, addresses[0], addresses[1], addresses[2], _stream()))
+
+
+def step_stats(desc, tensors, scalars, ring, state, workspace):
+    """stego_step_stats on torch's current stream: one launch; nothing is returned and nothing synchronises."""
+    _require_dev(ring, state, workspace, *tensors)
+    _require_dev(*scalars)
+    with _on_device(ring.device):
+        _check(step_stats_raw(desc, tensors, scalars, ring, state, workspace, _stream()))
 
 
 # ---- fused training tail of the two probes (include/stego_probe_train.h; stego_amd.probe_train wraps it for the trainer)

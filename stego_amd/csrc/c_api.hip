@@ -21,6 +21,7 @@
 #include "../../include/stego_salience.h"
 #include "../../include/stego_rec.h"
 #include "../../include/stego_render.h"
+#include "../../include/stego_stats.h"
 #include "corr_wide.h"
 #include "launchers.h"
 
@@ -383,6 +384,9 @@ const char* stego_error_string(int code)
         case STEGO_ERR_RENDER_FLAGS: return "render: unknown flag bit";
         case STEGO_ERR_RENDER_PARAM: return "render: alpha outside [0, 1], or a mean or std that is not finite";
         case STEGO_ERR_RENDER_SELECT: return "render: neither image nor labels selected, BLEND without both (or both without BLEND), EDGES without labels, or RESCALE without the image";
+        case STEGO_ERR_STATS_COUNT: return "step stats: n_tensors outside [1, 4], n_scalars outside [0, 16], or a count outside [0, 2^31) (include/stego_stats.h)";
+        case STEGO_ERR_STATS_RING: return "step stats: ring_slots outside [1, 65536]";
+        case STEGO_ERR_STATS_FLAGS: return "step stats: with_hist neither 0 nor 1";
         case STEGO_ERR_CRF_RANGE: return "dense CRF: a lattice coordinate would leave the packed key (image too large for its standard deviations)";
         default: return code >= STEGO_ERR_HIP ? "HIP runtime error (code - 1000 = hipError_t)" : "unknown error";
     }

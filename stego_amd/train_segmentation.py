@@ -136,6 +136,11 @@ class LitUnsupervisedSegmenter(nn.Module):
         self._reducer = None
         self._augmenter = None
         self._cluster_to_class = None
+        # cfg.train_log: the step's statistics stay on the device (stego_amd.step_stats) until the Trainer drains them into `train_log`
+        self.train_log = None            # a stego_amd.train_log.TrainLog, set by Trainer.fit
+        self._step_stats = None
+        self._stats_tags = None
+        self._stats_step0 = 0
 
     @property
     def label_cmap(self):
@@ -287,6 +292,7 @@ class LitUnsupervisedSegmenter(nn.Module):
         else:
             signal, signal_pos = feats, feats_pos
         loss = 0
+        stats_cd = None
         if cfg.use_salience:
             salience = batch["mask"].to(torch.float32).squeeze(1)
             salience_pos = batch["mask_pos"].to(torch.float32).squeeze(1)
@@ -303,9 +309,14 @@ class LitUnsupervisedSegmenter(nn.Module):
             self.log('loss/pos_intra', pos_intra_loss, **log_args)
             self.log('loss/pos_inter', pos_inter_loss, **log_args)
             self.log('loss/neg_inter', neg_inter_loss, **log_args)
-            self.log('cd/pos_intra', pos_intra_cd.mean(), **log_args)
-            self.log('cd/pos_inter', pos_inter_cd.mean(), **log_args)
-            self.log('cd/neg_inter', neg_inter_cd.mean(), **log_args)
+            if getattr(cfg, "train_log", False) and pos_intra_cd.is_cuda:
+                # one launch after the last loss term instead of three .mean() here: the means, and on histogram steps the buckets,
+                # go into the device ring (include/stego_stats.h); the cd/* entries of `logged` are those of the last drain
+                stats_cd = (pos_intra_cd, pos_inter_cd, neg_inter_cd)
+            else:
+                self.log('cd/pos_intra', pos_intra_cd.mean(), **log_args)
+                self.log('cd/pos_inter', pos_inter_cd.mean(), **log_args)
+                self.log('cd/neg_inter', neg_inter_cd.mean(), **log_args)
             loss += corr_total * cfg.correspondence_weight
 
         if cfg.rec_weight > 0:
@@ -351,6 +362,8 @@ class LitUnsupervisedSegmenter(nn.Module):
         loss += cluster_loss
         self.log('loss/cluster', cluster_loss, **log_args)
         self.log('loss/total', loss, **log_args)
+        if stats_cd is not None:
+            self._record_stats(stats_cd)
 
         self.manual_backward(loss)
         self.wait_gradients()
@@ -373,6 +386,42 @@ class LitUnsupervisedSegmenter(nn.Module):
                 self._optims[2] = torch.optim.Adam(list(self.cluster_probe.parameters()), lr=5e-3)
         self.global_step += 1
         return loss
+
+    def _record_stats(self, cd):
+        """cfg.train_log: the three cd tensors and every loss/* scalar of this step into the device ring, in one launch."""
+        if self._step_stats is None:
+            from .step_stats import StepStats
+            freq = max(int(getattr(self.cfg, "scalar_log_freq", 10)), 1)
+            self._stats_tags = [k for k, v in self.logged.items() if k.startswith("loss/") and torch.is_tensor(v) and v.is_cuda]
+            self._stats_step0 = self.global_step
+            self._step_stats = StepStats(len(self._stats_tags), min(max(freq, 4), 64), cd[0].device, n_tensors=3)
+        logged = self.logged
+        scalars = [logged[k] for k in self._stats_tags]          # (the terms a step logs follow from cfg: the same every step)
+        scalars = [v if v.dtype == torch.float32 and v.numel() == 1 else v.float().reshape(1) for v in scalars]
+        rank0 = self.train_log is None or self.train_log.writer is not None
+        with_hist = rank0 and self.train_log is not None and self.train_log.wants_hist(self.global_step)
+        self._step_stats.record([t if t.is_contiguous() else t.contiguous() for t in cd], scalars, with_hist)
+
+    @property
+    def stats_drain_every(self):
+        """Steps between two drains: cfg.scalar_log_freq, and no more than the ring holds."""
+        freq = max(int(getattr(self.cfg, "scalar_log_freq", 10)), 1)
+        return min(freq, self._step_stats.ring_slots) if self._step_stats is not None else freq
+
+    def drain_stats(self):
+        """One copy of the ring to the host: the cd/* entries of `logged` become the newest means, the records go to `train_log`."""
+        if self._step_stats is None:
+            return []
+        from .train_log import CD_TAGS
+        records = self._step_stats.drain()
+        for r in records:
+            r["step"] += self._stats_step0
+        if records:
+            for tag, t in zip(CD_TAGS, records[-1]["tensors"]):
+                self.logged[tag] = t["mean"]
+        if self.train_log is not None:
+            self.train_log.consume(records, self._stats_tags)
+        return records
 
     def validation_step(self, batch, batch_idx):
         img, label = batch["img"], batch["label"]
@@ -405,7 +454,28 @@ class LitUnsupervisedSegmenter(nn.Module):
         self.val_steps += 1
         for k, v in metrics.items():
             self.log(k, v)
+        if self.train_log is not None and self.train_log.writer is not None:
+            self._log_validation(outputs, metrics)
         return metrics
+
+    def _log_validation(self, outputs, metrics):
+        """cfg.train_log, rank 0: what the reference's validation_epoch_end writes (train_segmentation.py:285-330, 361-362) - the 4-row
+        sheet of the first validation batch as `plot_labels`, the column-normalised cluster histogram as `conf_matrix` when
+        cfg.has_labels and matplotlib is installed, and the metrics once global_step > 2.  (The label-frequency bars are not drawn.)"""
+        from .render import comparison_sheet
+        from .train_log import confusion_figure
+        if outputs:
+            o, cmap = outputs[0], self.label_cmap
+            sheet = comparison_sheet([{"image": o["img"], "rescale": True}, {"labels": o["label"], "cmap": cmap},
+                                      {"labels": o["linear_preds"], "cmap": cmap},
+                                      {"labels": o["cluster_preds"], "cmap": cmap, "mapping": self.cluster_metrics.cluster_to_class()}])
+            self.train_log.image("plot_labels", sheet, self.global_step)
+        if getattr(self.cfg, "has_labels", False) and hasattr(self.cluster_metrics, "histogram"):
+            fig = confusion_figure(self.cluster_metrics.histogram.cpu().numpy(), self.label_cmap)
+            if fig is not None:
+                self.train_log.image("conf_matrix", fig, self.global_step)
+        if self.global_step > 2:
+            self.train_log.scalars(metrics, self.global_step)
 
 
 class SyntheticContrastiveDataset(torch.utils.data.Dataset):
@@ -463,6 +533,10 @@ class Trainer:
                                  "(loader_crop_type=%r re-crops every epoch)" % crop)
             n_items = int(getattr(ds, "n_cache_items", len(ds)))
             model.net.enable_token_cache(n_items, (model.cfg.res, model.cfg.res), self.device)
+        logging = bool(getattr(model.cfg, "train_log", False)) and self.device.type == "cuda"
+        if logging and model.train_log is None:
+            from .train_log import TrainLog
+            model.train_log = TrainLog(model.cfg, self.rank)
         loader = self._shard_loader(loader)
         if len(loader) == 0:
             raise ValueError("empty loader (dataset of %d items, batch size %s, drop_last): nothing to train on"
@@ -486,7 +560,10 @@ class Trainer:
                 step += 1
                 if step % self.event_check_every == 0 or step >= self.max_steps:
                     self._check_loss_events(step)
-                if self.val_loader is not None and self.val_check_interval and step % self.val_check_interval == 0:
+                validating = self.val_loader is not None and self.val_check_interval and step % self.val_check_interval == 0
+                if logging and (step % model.stats_drain_every == 0 or validating or step >= self.max_steps):
+                    model.drain_stats()      # one copy of the ring per log interval: the only time the log waits for the device
+                if validating:
                     self._validate(model)
                 if step >= self.max_steps:
                     break

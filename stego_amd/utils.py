@@ -104,6 +104,7 @@ class UnsupervisedMetrics:
         else:
             hist = stats
         hist = hist.double()
+        self.histogram = hist          # the reordered matrix, as the reference's metric keeps it (utils.py:256): train_log draws it
         tp = torch.diag(hist)
         fp, fn = hist.sum(0) - tp, hist.sum(1) - tp
         iou = tp / (tp + fp + fn)
