@@ -6,27 +6,24 @@ repo snapshot.  No torch headers are involved: the library is plain C ABI.
 
 Every source is compiled to its own object (``stego_amd/lib/obj/*.o``, in parallel, only when it or a header
 changed) and the objects are linked into the one shared library: a one-kernel edit rebuilds in seconds.
+The sources are listed (``SOURCES``: the link order); the headers are found (every ``*.h`` of ``csrc/`` and ``include/``).
 """
+import functools
+import glob
 import os
+import re
 import shutil
 import subprocess
+import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
+INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB_DIR = os.path.join(HERE, "lib")
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 LIB_PATH = os.path.join(LIB_DIR, "libstego_corr.so")
 SOURCES = ["corr_sample.hip", "corr_fwd.hip", "corr_fused.hip", "corr_fused_odd.hip", "corr_fused_c192.hip", "corr_fused_half.hip", "corr_bwd.hip", "corr_bwd_lists.hip", "knn_topk.hip", "dense_corr.hip", "dense_stream.hip", "sample_sets.hip", "loss_pointwise.hip", "corr_wide.hip", "vit_forward.hip", "host_util.hip", "draws.hip", "head_fused.hip", "dense_crf.hip", "batch_prep.hip", "batch_prep_dir.hip", "salience_draw.hip", "probe_head.hip", "probe_train.hip", "corr_pr.hip", "corr_heat.hip", "crf_loss.hip", "augment.hip", "confusion.hip", "optim_step.hip", "stitch_probe.hip", "rec_loss.hip", "render.hip", "step_stats.hip", "c_api.hip"]
-HEADERS = ["corr_common.h", "corr_consts.h", "corr_bwd_plan.h", "corr_bwd_tile.h", "probe_common.h", "probe_phases.h", "addon_device.h", "corr_tile.h", "host_util.h", "dispatch.h", "ws_layout.h", "launchers.h", "corr_wide.h", "corr_fused_kernel.h", "vit_gemm_tile.h", os.path.join("..", "..", "include", "stego_corr.h"), os.path.join("..", "..", "include", "stego_vit.h"),
-           os.path.join("..", "..", "include", "stego_head.h"), os.path.join("..", "..", "include", "stego_crf.h"),
-           os.path.join("..", "..", "include", "stego_data.h"), os.path.join("..", "..", "include", "stego_probe.h"),
-           os.path.join("..", "..", "include", "stego_pr.h"), os.path.join("..", "..", "include", "stego_probe_train.h"),
-           os.path.join("..", "..", "include", "stego_heat.h"), os.path.join("..", "..", "include", "stego_crf_loss.h"),
-           os.path.join("..", "..", "include", "stego_aug.h"), os.path.join("..", "..", "include", "stego_confusion.h"),
-           os.path.join("..", "..", "include", "stego_optim.h"), os.path.join("..", "..", "include", "stego_stitch.h"),
-           os.path.join("..", "..", "include", "stego_salience.h"), os.path.join("..", "..", "include", "stego_rec.h"),
-           os.path.join("..", "..", "include", "stego_render.h"), os.path.join("..", "..", "include", "stego_stats.h")]
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 LDFLAGS = ["--offload-arch=gfx950", "-fPIC", "-shared"]
 # the one torch C++ extension (host only, g++): the autograd function of the loss and the generator's graph-safe Philox state, over the C ABI
@@ -37,27 +34,39 @@ TORCHGLUE_SRC = os.path.join(CSRC, "torch_glue_ext.cpp")
 TORCHGLUE_PATH = os.path.join(LIB_DIR, "_stego_torchglue.so")
 
 
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+
+def have_hipcc():
+    """Whether this machine can compile the kernels at all: what the build-time guards of tests/ skip on."""
+    return os.path.exists(HIPCC)
+
+
 def _hipcc():
-    exe = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(exe):
+    if not have_hipcc():
         raise RuntimeError("hipcc not found (need ROCm with gfx950 support)")
-    return exe
+    return HIPCC
 
 
 def sources():
-    return [os.path.join(CSRC, s) for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
+    srcs = [os.path.join(CSRC, s) for s in SOURCES]
+    missing = [s for s in srcs if not os.path.exists(s)]
+    if missing:
+        raise RuntimeError("SOURCES names files that do not exist: " + ", ".join(missing))
+    return srcs
 
 
 def _headers():
-    return [p for p in (os.path.join(CSRC, h) for h in HEADERS) if os.path.exists(p)]
+    return sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(INCLUDE, "*.h")))
 
 
-def _obj(src):
-    return os.path.join(OBJ_DIR, os.path.splitext(os.path.basename(src))[0] + ".o")
+def _obj(src, odir=None):
+    return os.path.join(odir or OBJ_DIR, os.path.splitext(os.path.basename(src))[0] + ".o")
 
 
-def _obj_stale(src):
-    o = _obj(src)
+def _obj_stale(src, odir=None):
+    """An object is stale when its source, any header or this file is newer than it."""
+    o = _obj(src, odir)
     if not os.path.exists(o):
         return True
     t = os.path.getmtime(o)
@@ -71,15 +80,33 @@ def is_stale():
     return any(os.path.getmtime(d) > t for d in sources() + _headers())
 
 
-def _compile(src, extra, verbose):
-    cmd = [_hipcc()] + CFLAGS + list(extra) + ["-c", src, "-o", _obj(src) + ".tmp"]
+def _run(cmd, what, verbose):
     if verbose:
         print(" ".join(cmd))
     res = subprocess.run(cmd, capture_output=True, text=True)
     if res.returncode != 0:
-        raise RuntimeError("hipcc failed on %s:\n%s%s" % (src, res.stdout, res.stderr))
-    os.replace(_obj(src) + ".tmp", _obj(src))
+        raise RuntimeError("%s failed:\n%s%s" % (what, res.stdout, res.stderr))
     return res.stderr
+
+
+def _compile_objects(srcs, odir, flags, force, verbose):
+    """Compile the stale ones of `srcs` (all of them with `force`) into `odir`, in parallel; returns the sources it compiled."""
+    os.makedirs(odir, exist_ok=True)
+    todo = [s for s in srcs if force or _obj_stale(s, odir)]
+
+    def one(src):
+        _run([_hipcc()] + flags + ["-c", src, "-o", _obj(src, odir) + ".tmp"], "hipcc on " + src, verbose)
+        os.replace(_obj(src, odir) + ".tmp", _obj(src, odir))
+
+    with ThreadPoolExecutor(max_workers=min(8, max(1, len(todo)))) as ex:
+        list(ex.map(one, todo))
+    return todo
+
+
+def _link(inputs, flags, out, verbose):
+    _run([_hipcc()] + flags + inputs + ["-o", out + ".tmp"], "hipcc link", verbose)
+    os.replace(out + ".tmp", out)
+    return out
 
 
 def build(force=False, verbose=False, extra_flags=(), out=None):
@@ -91,23 +118,9 @@ def build(force=False, verbose=False, extra_flags=(), out=None):
     os.makedirs(OBJ_DIR, exist_ok=True)
     srcs = sources()
     if extra_flags:                       # one-off variant build: everything in one go, no cache
-        cmd = [_hipcc()] + CFLAGS + list(extra_flags) + ["-shared"] + srcs + ["-o", out + ".tmp"]
-        res = subprocess.run(cmd, capture_output=True, text=True)
-        if res.returncode != 0:
-            raise RuntimeError("hipcc failed:\n" + res.stdout + res.stderr)
-        os.replace(out + ".tmp", out)
-        return out
-    todo = [s for s in srcs if force or _obj_stale(s)]
-    with ThreadPoolExecutor(max_workers=min(8, max(1, len(todo)))) as ex:
-        list(ex.map(lambda s: _compile(s, (), verbose), todo))
-    cmd = [_hipcc()] + LDFLAGS + [_obj(s) for s in srcs] + ["-o", out + ".tmp"]
-    if verbose:
-        print(" ".join(cmd))
-    res = subprocess.run(cmd, capture_output=True, text=True)
-    if res.returncode != 0:
-        raise RuntimeError("hipcc link failed:\n" + res.stdout + res.stderr)
-    os.replace(out + ".tmp", out)
-    return out
+        return _link(srcs, CFLAGS + list(extra_flags) + ["-shared"], out, False)
+    _compile_objects(srcs, OBJ_DIR, CFLAGS, force, verbose)
+    return _link([_obj(s) for s in srcs], LDFLAGS, out, verbose)
 
 
 def build_torchglue(force=False, verbose=False):
@@ -150,7 +163,6 @@ ASAN_FLAGS = ["-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-share
 
 def asan_runtime():
     """The clang AddressSanitizer runtime to LD_PRELOAD into an uninstrumented python (None if this toolchain has none)."""
-    import glob
     hits = sorted(glob.glob(os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(_hipcc()))), "lib", "llvm", "lib", "clang", "*", "lib", "linux",
                                          "libclang_rt.asan-x86_64.so")))
     return hits[-1] if hits else None
@@ -159,41 +171,11 @@ def asan_runtime():
 def build_asan(force=False, verbose=False):
     """lib/asan/libstego_corr.so: every source with ASAN_FLAGS (objects cached under lib/obj/asan)."""
     odir = os.path.join(OBJ_DIR, "asan")
-    os.makedirs(odir, exist_ok=True)
     os.makedirs(ASAN_DIR, exist_ok=True)
     srcs = sources()
-    deps = _headers() + [os.path.abspath(__file__)]
-
-    def obj(src):
-        return os.path.join(odir, os.path.splitext(os.path.basename(src))[0] + ".o")
-
-    def stale(src):
-        o = obj(src)
-        return force or not os.path.exists(o) or any(os.path.getmtime(d) > os.path.getmtime(o) for d in [src] + deps)
-
-    def one(src):
-        cmd = [_hipcc()] + CFLAGS + ASAN_FLAGS + ["-c", src, "-o", obj(src) + ".tmp"]
-        if verbose:
-            print(" ".join(cmd))
-        res = subprocess.run(cmd, capture_output=True, text=True)
-        if res.returncode != 0:
-            raise RuntimeError("hipcc (asan) failed on %s:\n%s%s" % (src, res.stdout, res.stderr))
-        os.replace(obj(src) + ".tmp", obj(src))
-
-    todo = [s for s in srcs if stale(s)]
-    with ThreadPoolExecutor(max_workers=min(8, max(1, len(todo)))) as ex:
-        list(ex.map(one, todo))
-    if todo or not os.path.exists(ASAN_LIB_PATH):
-        res = subprocess.run([_hipcc()] + LDFLAGS + ASAN_FLAGS + [obj(s) for s in srcs] + ["-o", ASAN_LIB_PATH + ".tmp"], capture_output=True, text=True)
-        if res.returncode != 0:
-            raise RuntimeError("hipcc link (asan) failed:\n" + res.stdout + res.stderr)
-        os.replace(ASAN_LIB_PATH + ".tmp", ASAN_LIB_PATH)
+    if _compile_objects(srcs, odir, CFLAGS + ASAN_FLAGS, force, verbose) or not os.path.exists(ASAN_LIB_PATH):
+        _link([_obj(s, odir) for s in srcs], LDFLAGS + ASAN_FLAGS, ASAN_LIB_PATH, verbose)
     return ASAN_LIB_PATH
-
-
-if __name__ == "__main__":
-    print(build(force=True, verbose=True))
-    print(build_torchglue(force=True, verbose=True))
 
 
 def build_skeleton(force=False, verbose=False):
@@ -204,9 +186,47 @@ def build_skeleton(force=False, verbose=False):
     if not force and os.path.exists(SKELETON_PATH) and os.path.getmtime(SKELETON_PATH) >= os.path.getmtime(src):
         return SKELETON_PATH
     os.makedirs(LIB_DIR, exist_ok=True)
-    cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", src, "-o", SKELETON_PATH + ".tmp"]
+    cmd = [_hipcc()] + CFLAGS[:3] + [src, "-o", SKELETON_PATH + ".tmp"]      # architecture, optimisation, standard: the library's
     if verbose:
         print(" ".join(cmd))
     subprocess.run(cmd, check=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     os.replace(SKELETON_PATH + ".tmp", SKELETON_PATH)
     return SKELETON_PATH
+
+
+# ---- what the compiler reports per kernel (registers, spills, scratch, occupancy, LDS): the build-time guards of tests/ read it from here,
+# so they see the compilation that ships (CFLAGS)
+def parse_resource_remarks(text):
+    """{mangled function name: {remark name: int}} from the stderr of a -Rpass-analysis=kernel-resource-usage compile."""
+    kernels, name = {}, None
+    for line in text.splitlines():
+        m = re.search(r"remark: Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            kernels[name] = {}
+            continue
+        m = re.search(r"remark:\s+([^:]+): (\d+)\b", line)
+        if m and name:
+            kernels[name][m.group(1)] = int(m.group(2))
+    return kernels
+
+
+@functools.lru_cache(maxsize=None)
+def kernel_resources(source_name):
+    """The resource figures of every kernel of csrc/<source_name>, compiled with CFLAGS into a temporary directory (once per process).
+    --cuda-device-only leaves out the host pass, which reports nothing: the table of all 35 sources is the same with and without it."""
+    with tempfile.TemporaryDirectory() as tmp:
+        cmd = [_hipcc()] + CFLAGS + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, source_name),
+                                     "-o", os.path.join(tmp, "unit.o")]
+        return parse_resource_remarks(_run(cmd, "hipcc on " + source_name, False))
+
+
+def kernel_resources_each(source_names):
+    """[kernel_resources(s) for s in source_names], the units compiled side by side."""
+    with ThreadPoolExecutor(max_workers=min(8, len(source_names))) as ex:
+        return list(ex.map(kernel_resources, source_names))
+
+
+if __name__ == "__main__":
+    print(build(force=True, verbose=True))
+    print(build_torchglue(force=True, verbose=True))

@@ -14,10 +14,10 @@ import pytest
 
 import bwd_variant_cases as T
 from oracle import corr_oracle as O
+from stego_amd import _build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GXX = shutil.which("g++")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 # short name in the table -> the __global__ function template
 FUNCTIONS = {"tile_build": "corr_bwd_tile_build_kernel", "tile32_build": "corr_bwd_tile32_build_kernel", "tile_h": "corr_bwd_tile_h_kernel",
@@ -137,7 +137,7 @@ def test_the_table_is_well_formed():
     assert any(c.name == T.AFTER_REFUSAL for c in T.CASES)
 
 
-@pytest.mark.skipif(GXX is None or not os.path.exists(HIPCC), reason="needs g++ and hipcc")
+@pytest.mark.skipif(GXX is None or not _build.have_hipcc(), reason="needs g++ and hipcc")
 def test_every_row_names_the_plan_s_kernels_and_the_table_reaches_every_emitted_kernel(tmp_path):
     out = _run_program(tmp_path)
     reached = {line.split(" ", 1)[1] for line in out.splitlines() if line.startswith("REACHED ")}
@@ -147,21 +147,10 @@ def test_every_row_names_the_plan_s_kernels_and_the_table_reaches_every_emitted_
     assert bands["band-f16x3-W66-K128"][:3] == (2, 3, 5) and bands["band-f16x3-W192-K128"] == (1, 3, 3, 98304), bands
 
     # the two units, compiled exactly as test_backward_kernels_do_not_spill compiles them
-    from concurrent.futures import ThreadPoolExecutor
-
-    def compile_one(name):
-        src = os.path.join(ROOT, "stego_amd", "csrc", name)
-        cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", os.path.join(ROOT, "stego_amd", "csrc"),
-               "-I", os.path.join(ROOT, "include"), "-c", src, "-o", str(tmp_path / (name + ".o")), "-Rpass-analysis=kernel-resource-usage"]
-        return subprocess.run(cmd, capture_output=True, text=True, cwd=str(tmp_path))
-
-    with ThreadPoolExecutor(2) as ex:
-        results = list(ex.map(compile_one, ["corr_bwd.hip", "corr_bwd_lists.hip"]))
     by_function = {v: k for k, v in FUNCTIONS.items()}
     emitted = set()
-    for res in results:
-        assert res.returncode == 0, res.stderr[-2000:]
-        for mangled in re.findall(r"Function Name: (\S+)", res.stderr):
+    for unit in _build.kernel_resources_each(["corr_bwd.hip", "corr_bwd_lists.hip"]):
+        for mangled in unit:
             m = re.match(r"_ZN5stego(\d+)", mangled)
             assert m, mangled
             fn = mangled[m.end():m.end() + int(m.group(1))]

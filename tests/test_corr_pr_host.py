@@ -3,9 +3,6 @@ computed (tests/golden/corr_pr_small.npz, tools/make_pr_golden.py), the curve ar
 stego_pr_accumulate (include/stego_pr.h), and the kernel's compiled resources."""
 import ctypes
 import os
-import re
-import shutil
-import subprocess
 import warnings
 
 import numpy as np
@@ -14,11 +11,10 @@ import torch
 
 import corr_pr_oracle as P
 from conftest import load_golden
-from stego_amd import capi
+from stego_amd import _build, capi
 from stego_amd.correspondence_pr import CorrespondencePR, pr_from_hist
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 A = 0x10000          # a 256-byte aligned stand-in address: the checks reject before any pointer is read
 
 
@@ -221,22 +217,9 @@ def test_python_surface_refuses_cpu_tensors():
 
 
 # ------------------------------------------------------------------ 4. compiled resources
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_corr_pr_kernel_has_no_spills(tmp_path):
-    src = os.path.join(ROOT, "stego_amd", "csrc", "corr_pr.hip")
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", src, "-o", str(tmp_path / "corr_pr.o"), "-Rpass-analysis=kernel-resource-usage"]
-    res = subprocess.run(cmd, capture_output=True, text=True, cwd=str(tmp_path))
-    assert res.returncode == 0, res.stderr[-2000:]
-    kernels, name = {}, None
-    for line in res.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs Spill|SGPRs Spill|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and name:
-            kernels[name][m.group(1)] = int(m.group(2))
+@pytest.mark.skipif(not _build.have_hipcc(), reason="needs hipcc")
+def test_corr_pr_kernel_has_no_spills():
+    kernels = _build.kernel_resources("corr_pr.hip")
     pr = {k: v for k, v in kernels.items() if "corr_pr_kernel" in k}
     assert len(pr) == 1, sorted(kernels)                   # one instantiation: flags and shapes are run-time parameters
     for k, v in pr.items():

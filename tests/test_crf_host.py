@@ -2,19 +2,13 @@
 properties, the reference's image conversion, the host-side checks of stego_amd.crf and of the C ABI (include/stego_crf.h), and the
 register / spill guard of csrc/dense_crf.hip."""
 import ctypes
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import crf_oracle as O
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from stego_amd import _build
 
 
 def _lattice_vs_exact(d, scale, seed=0, n=1500):
@@ -145,25 +139,11 @@ def test_workspace_bytes_and_error_codes_through_ctypes():
     assert b"dense CRF" in lib.stego_error_string(capi.CRF_ERR_RANGE)
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_crf_kernels_do_not_spill(tmp_path):
+@pytest.mark.skipif(not _build.have_hipcc(), reason="needs hipcc")
+def test_crf_kernels_do_not_spill():
     """Every kernel of csrc/dense_crf.hip keeps its working set in registers (the embedding's per-pixel arrays are indexed by
     unrolled compares, not through private memory) at full occupancy but for the combine kernel."""
-    src = os.path.join(ROOT, "stego_amd", "csrc", "dense_crf.hip")
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-c", src,
-           "-o", str(tmp_path / "crf.o"), "-Rpass-analysis=kernel-resource-usage"]
-    res = subprocess.run(cmd, capture_output=True, text=True, cwd=str(tmp_path))
-    assert res.returncode == 0, res.stderr[-2000:]
-    kernels, name = {}, None
-    for line in res.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs Spill|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and name:
-            kernels[name][m.group(1)] = int(m.group(2))
+    kernels = _build.kernel_resources("dense_crf.hip")
     ours = {k: v for k, v in kernels.items() if "9stego_crf" in k}
     # embed / emit / neighbours x 2 lattices, count, scan, norm x 2, splat / blur x 2 / unary / combine x 5 group widths
     assert len(ours) == 3 * 2 + 2 + 2 + 5 * 5, sorted(ours)

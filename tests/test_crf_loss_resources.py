@@ -4,37 +4,18 @@ scratch, and keeps the occupancy it has today.
 Today (waves/SIMD from the compiler's register count): crf_prepare 8 (48 VGPRs), crf_finish 8 (24); crf_pairs<NT, backward> for
 KP = 32 NT channels: <1, 1> 3 (150), <2, 1> 3 (166), <3, 1> 2 (207; K = 70, the training shape: two workgroups of four waves per
 compute unit), <4, 1> 2 (243); forward only <1, 0> 4 (105), <2, 0> 3 (130), <3, 0> 3 (138), <4, 0> 3 (156)."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from stego_amd import _build
+
 OCCUPANCY_FLOOR = {"crf_prepare": 8, "crf_finish": 8, "crf_pairsILi1ELb1E": 3, "crf_pairsILi2ELb1E": 3, "crf_pairsILi3ELb1E": 2,
                    "crf_pairsILi4ELb1E": 2, "crf_pairsILi1ELb0E": 4, "crf_pairsILi2ELb0E": 3, "crf_pairsILi3ELb0E": 3,
                    "crf_pairsILi4ELb0E": 3}
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_crf_loss_kernels_have_no_spills(tmp_path):
-    src = os.path.join(ROOT, "stego_amd", "csrc", "crf_loss.hip")
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-c", src, "-o",
-           str(tmp_path / "crf_loss.o"), "-Rpass-analysis=kernel-resource-usage"]
-    res = subprocess.run(cmd, capture_output=True, text=True, cwd=str(tmp_path))
-    assert res.returncode == 0, res.stderr[-2000:]
-    kernels, name = {}, None
-    for line in res.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs Spill|SGPRs Spill|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and name:
-            kernels[name][m.group(1)] = int(m.group(2))
+@pytest.mark.skipif(not _build.have_hipcc(), reason="needs hipcc")
+def test_crf_loss_kernels_have_no_spills():
+    kernels = _build.kernel_resources("crf_loss.hip")
     crf = {k: v for k, v in kernels.items() if "crf_" in k}
     assert len(crf) == len(OCCUPANCY_FLOOR), sorted(kernels)
     for k, v in crf.items():

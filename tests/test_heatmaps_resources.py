@@ -1,33 +1,13 @@
 """Build-time guard for csrc/corr_heat.hip: the low-resolution kernel and both instantiations of the write kernel (16-byte and
 4-byte stores) compile for gfx950 with no VGPR / SGPR spills and no scratch, and keep the occupancy they have today."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from stego_amd import _build
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_heatmap_kernels_have_no_spills(tmp_path):
-    src = os.path.join(ROOT, "stego_amd", "csrc", "corr_heat.hip")
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", src, "-o", str(tmp_path / "corr_heat.o"),
-           "-Rpass-analysis=kernel-resource-usage"]
-    res = subprocess.run(cmd, capture_output=True, text=True, cwd=str(tmp_path))
-    assert res.returncode == 0, res.stderr[-2000:]
-    kernels, name = {}, None
-    for line in res.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs Spill|SGPRs Spill|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and name:
-            kernels[name][m.group(1)] = int(m.group(2))
+@pytest.mark.skipif(not _build.have_hipcc(), reason="needs hipcc")
+def test_heatmap_kernels_have_no_spills():
+    kernels = _build.kernel_resources("corr_heat.hip")
     low = {k: v for k, v in kernels.items() if "heat_low_kernel" in k}
     write = {k: v for k, v in kernels.items() if "heat_write_kernel" in k}
     assert len(low) == 1 and len(write) == 2, sorted(kernels)      # flags and shapes are run-time parameters; the store width is not

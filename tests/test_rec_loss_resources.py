@@ -5,37 +5,18 @@ Today (waves/SIMD as the compiler reports them): rec_tiles<1> 2 (228 VGPRs), rec
 waves, one per SIMD, and its LDS, up to 151 KiB of dynamic memory sized by C at the launch, allows one workgroup per compute unit at
 C = 1024 and two at C = 384); rec_finish<1 .. 4> 3, 2, 2, 1 (128, 140, 160, 179 VGPRs; 18,952 to 68,104 bytes of static LDS: the waves'
 code tiles, then their sums)."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from stego_amd import _build
+
 OCCUPANCY_FLOOR = {"rec_tiles": 1, "rec_finish": 1}
 LDS_CEILING = {"rec_tiles": 0, "rec_finish": 68104}           # static bytes: rec_tiles' LDS is dynamic (stego_rec_loss_plan reports it)
 INSTANCES = {"rec_tiles": 4, "rec_finish": 4}
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_rec_loss_kernels_have_no_spills(tmp_path):
-    src = os.path.join(ROOT, "stego_amd", "csrc", "rec_loss.hip")
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-c", src, "-o",
-           str(tmp_path / "rec_loss.o"), "-Rpass-analysis=kernel-resource-usage"]
-    res = subprocess.run(cmd, capture_output=True, text=True, cwd=str(tmp_path))
-    assert res.returncode == 0, res.stderr[-2000:]
-    kernels, name = {}, None
-    for line in res.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs Spill|SGPRs Spill|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name:
-            kernels[name][m.group(1)] = int(m.group(2))
+@pytest.mark.skipif(not _build.have_hipcc(), reason="needs hipcc")
+def test_rec_loss_kernels_have_no_spills():
+    kernels = _build.kernel_resources("rec_loss.hip")
     ours = {k: v for k, v in kernels.items() if any(key in k for key in OCCUPANCY_FLOOR)}
     assert len(ours) == sum(INSTANCES.values()), sorted(kernels)
     for k, v in sorted(ours.items()):

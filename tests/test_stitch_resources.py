@@ -5,15 +5,10 @@ and the plan that sizes that LDS stays within its 64 KiB budget.
 
 Today: 96 / 158 / 198 VGPRs at 8 / 16 / 32 slots (5 / 3 / 2 waves per SIMD); at 64 slots 170 / 170 (one window) and 182 / 196
 (several) for the linear / cluster probe, 2 waves."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from stego_amd import _build
+
 LDS_BUDGET = 64 * 1024
 INSTANCES = {"slots8": "stitch_probe_kernelILi8ELb1ELb1E", "slots16": "stitch_probe_kernelILi16ELb1ELb1E",
              "slots32": "stitch_probe_kernelILi32ELb1ELb1E", "slots64_linear_sole": "stitch_probe_kernelILi64ELb1ELb0ELi1E",
@@ -21,37 +16,16 @@ INSTANCES = {"slots8": "stitch_probe_kernelILi8ELb1ELb1E", "slots16": "stitch_pr
              "slots64_cluster_blend": "stitch_probe_kernelILi64ELb0ELb1ELi2E", "gather": "window_gather_kernel"}
 
 
-@pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
-    """name -> resource figures of every kernel of stitch_probe.hip, from one compilation."""
-    if not os.path.exists(HIPCC):
-        pytest.skip("needs hipcc")
-    tmp = tmp_path_factory.mktemp("stitch")
-    src = os.path.join(ROOT, "stego_amd", "csrc", "stitch_probe.hip")
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-c", src, "-o",
-           str(tmp / "stitch_probe.o"), "-Rpass-analysis=kernel-resource-usage"]
-    res = subprocess.run(cmd, capture_output=True, text=True, cwd=str(tmp))
-    assert res.returncode == 0, res.stderr[-2000:]
-    out, name = {}, None
-    for line in res.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs Spill|SGPRs Spill|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|"
-                      r"LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name:
-            out[name][m.group(1)] = int(m.group(2))
-    return out
-
-
-def test_every_instantiation_is_there(kernels):
+@pytest.mark.skipif(not _build.have_hipcc(), reason="needs hipcc")
+def test_every_instantiation_is_there():
+    kernels = _build.kernel_resources("stitch_probe.hip")
     assert sum("stitch_probe_kernel" in k for k in kernels) == 7 and sum("window_gather_kernel" in k for k in kernels) == 1, sorted(kernels)
 
 
+@pytest.mark.skipif(not _build.have_hipcc(), reason="needs hipcc")
 @pytest.mark.parametrize("inst", sorted(INSTANCES))
-def test_stitch_kernel_has_no_spills(kernels, inst):
+def test_stitch_kernel_has_no_spills(inst):
+    kernels = _build.kernel_resources("stitch_probe.hip")
     hits = [v for k, v in kernels.items() if INSTANCES[inst] in k]
     assert len(hits) == 1, (inst, sorted(kernels))
     v = hits[0]

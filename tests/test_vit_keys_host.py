@@ -3,15 +3,11 @@ the symbol and the ABI version, its argument checks - the same codes in the same
 any device call (the pointers below are made-up addresses, never dereferenced) - and the torch fallback of a "KK" featurizer on
 the CPU."""
 import ctypes
-import os
-import re
-import shutil
-import subprocess
 
 import pytest
 import torch
 
-from stego_amd import capi, dino_vit
+from stego_amd import _build, capi, dino_vit
 
 OK, ERR_NULL, ERR_SHAPE, ERR_UNSUPPORTED, ERR_WORKSPACE, ERR_ALIGN = 0, 1, 2, 3, 4, 5      # include/stego_corr.h
 FAKE = 0x7F0000001000            # 4 KiB aligned, non-null
@@ -73,28 +69,11 @@ def test_every_width_keeps_the_key_columns_inside_the_packed_qkv_weight():
         assert _call("stego_vit_forward_keys", _desc(D=D, heads=D // 64, hidden=D), ws_bytes=0) == ERR_WORKSPACE, D
 
 
-def test_the_keys_kernel_keeps_the_register_budget_of_the_gemm(tmp_path):
+@pytest.mark.skipif(not _build.have_hipcc(), reason="needs hipcc")
+def test_the_keys_kernel_keeps_the_register_budget_of_the_gemm():
     """vit_keys_kernel is the GEMM tile of vit_gemm_kernel with another epilogue: like it, two 512-thread workgroups per CU
     (occupancy >= 4 waves per SIMD) and nothing spilled inside the k loop (tests/test_kernel_resources.py: at most 8 registers)."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = os.path.join(root, "stego_amd", "csrc", "vit_forward.hip")
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-c", src, "-o", str(tmp_path / "vit.o"),
-           "-Rpass-analysis=kernel-resource-usage"]
-    res = subprocess.run(cmd, capture_output=True, text=True, cwd=str(tmp_path))
-    assert res.returncode == 0, res.stderr[-2000:]
-    kernels, name = {}, None
-    for line in res.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and name:
-            kernels[name][m.group(1)] = int(m.group(2))
+    kernels = _build.kernel_resources("vit_forward.hip")
     keys = {k: v for k, v in kernels.items() if "vit_keys_kernel" in k}
     assert len(keys) == 2, sorted(kernels)                       # two precisions
     for k, v in keys.items():

@@ -14,10 +14,10 @@ import numpy as np
 import pytest
 
 import wide_variant_cases as T
+from stego_amd import _build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GXX = shutil.which("g++")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 # every row and stage case by name: a row that leaves the table, or joins it, does so here too - on purpose
 ROWS = """
@@ -211,7 +211,7 @@ def test_every_row_names_the_plan_s_variants_and_the_table_reaches_every_variant
     assert len(run.stdout.split("PANEL ")) - 1 == len(T.PANELS)
 
 
-@pytest.mark.skipif(GXX is None or not os.path.exists(HIPCC), reason="needs g++ and hipcc")
+@pytest.mark.skipif(GXX is None or not _build.have_hipcc(), reason="needs g++ and hipcc")
 def test_the_table_reaches_every_kernel_the_sampler_and_gemm_units_emit(tmp_path):
     """The instantiations hipcc emits for sample_sets.hip and dense_corr.hip, by their mangled names: every sample_panels_kernel<VW1, VW2>
     and every GEMM on prepared operands has a row or a stage case (the four-stage ring of the row-block kernel is a tool's, behind a debug bit;
@@ -219,12 +219,8 @@ def test_the_table_reaches_every_kernel_the_sampler_and_gemm_units_emit(tmp_path
     run = _build_and_run(tmp_path, T.CASES, T.PANELS)
     reached = {line.split(" ", 1)[1] for line in run.stdout.splitlines() if line.startswith("REACHED ")}
     emitted, others = set(), set()
-    for unit in ("sample_sets.hip", "dense_corr.hip"):
-        cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", os.path.join(ROOT, "stego_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-               "-c", os.path.join(ROOT, "stego_amd", "csrc", unit), "-o", str(tmp_path / (unit + ".o")), "-Rpass-analysis=kernel-resource-usage"]
-        res = subprocess.run(cmd, capture_output=True, text=True, cwd=str(tmp_path))
-        assert res.returncode == 0, res.stderr[-2000:]
-        for mangled in set(re.findall(r"Function Name: (\S+)", res.stderr)):
+    for unit in _build.kernel_resources_each(["sample_sets.hip", "dense_corr.hip"]):
+        for mangled in unit:
             m = re.match(r"_ZN5stego(\d+)", mangled)
             assert m, mangled
             fn = mangled[m.end():m.end() + int(m.group(1))]

@@ -2,7 +2,7 @@
 """Round 5: a variant of the library that differs only in the fused forward's three translation units (compiled in parallel with the
 given -D flags), linked with the cached objects of everything else:  tools/exp/build_fused_variant.py NAME [-DFLAG ...]  ->  stego_amd/lib/NAME.so
 Prints the register / spill / scratch numbers of the headline instantiation (f16x3, C = 384, K <= 96, even)."""
-import os, re, subprocess, sys
+import os, subprocess, sys
 from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -34,15 +34,9 @@ def main():
     res = subprocess.run([_build._hipcc()] + _build.LDFLAGS + objs + ["-o", out], capture_output=True, text=True)
     if res.returncode != 0:
         sys.exit(res.stderr[-4000:])
-    cur, stats, worst = None, {}, (0, "")
+    stats, worst = {}, (0, "")
     for _, err in outs:
-        for line in err.splitlines():
-            m = re.search(r"Function Name: (\S+)", line)
-            if m:
-                cur = m.group(1); stats[cur] = {}; continue
-            m = re.search(r"remark:\s+(VGPRs Spill|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill): (\d+)", line)
-            if m and cur:
-                stats[cur][m.group(1)] = int(m.group(2))
+        stats.update(_build.parse_resource_remarks(err))
     for k, v in stats.items():
         if "corr_fused_kernel" in k and v.get("VGPRs Spill", 0) > worst[0]:
             worst = (v["VGPRs Spill"], k)
