@@ -246,6 +246,22 @@ RENDER_I64, RENDER_I32, RENDER_U8 = 0, 1, 2
 RENDER_DTYPES = {torch.int64: RENDER_I64, torch.int32: RENDER_I32, torch.uint8: RENDER_U8}
 RENDER_MAX_LUT, RENDER_MAX_B = 512, 65535
 
+
+class StegoPcaDesc(Structure):
+    """include/stego_pca.h"""
+    _fields_ = [(n, c_int32) for n in ("B", "C", "h", "w", "H", "W", "group", "n_iter", "resize", "scale")] + \
+        [(n, c_int64) for n in ("out_stride_n", "out_stride_h")]
+
+
+PCA_ERR_DIM, PCA_ERR_SIZE, PCA_ERR_ITER, PCA_ERR_MODE = 170, 171, 172, 173
+PCA_PER_IMAGE, PCA_JOINT = 0, 1
+PCA_BILINEAR, PCA_NEAREST = 0, 1
+PCA_UNIT, PCA_RANGE = 0, 1
+PCA_RESIZES = {"bilinear": PCA_BILINEAR, "nearest": PCA_NEAREST}
+PCA_SCALES = {"unit": PCA_UNIT, "range": PCA_RANGE}
+PCA_MIN_C, PCA_MAX_C, PCA_MAX_B, PCA_MAX_SIDE, PCA_MAX_TOKENS, PCA_MIN_TOKENS = 3, 768, 65535, 4096, 1 << 28, 4
+PCA_MAX_ITER, PCA_DEFAULT_ITER, PCA_FOLD = 256, 32, 1024
+
 # name -> (restype, argtypes); every symbol include/stego_corr.h declares
 _P = c_void_p
 _H = POINTER(StegoHeadDesc)
@@ -278,6 +294,10 @@ SIGNATURES = {
     "stego_image_range_workspace_bytes": (c_size_t, [POINTER(StegoRenderDesc)]),
     "stego_image_range": (c_int32, [POINTER(StegoRenderDesc), _M, _P, _P, c_size_t, _P]),
     "stego_render": (c_int32, [POINTER(StegoRenderDesc), _M, _P, _P, _P, _P, _P]),
+    "stego_pca_workspace_bytes": (c_size_t, [POINTER(StegoPcaDesc)]),
+    "stego_pca_fit": (c_int32, [POINTER(StegoPcaDesc), _M, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "stego_pca_scores": (c_int32, [POINTER(StegoPcaDesc), _M, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "stego_pca_paint": (c_int32, [POINTER(StegoPcaDesc), _P, _P, _P, _P]),
     "stego_probe_confusion": (c_int32, [POINTER(StegoProbeConfusionDesc), _M, _M] + [_P] * 6 + [_P]),
     "stego_probe_confusion_plan": (c_size_t, [POINTER(StegoProbeConfusionDesc), POINTER(c_int32), POINTER(c_int32)]),
     "stego_confusion": (c_int32, [POINTER(StegoConfusionDesc), _P, _P, _P, _P]),
@@ -1457,6 +1477,78 @@ def render(desc, image, labels, lut, rng, out):
     _require_dev(image, labels, lut, rng, out)
     with _on_device(out.device):
         _check(render_raw(desc, _map(image) if image is not None else None, labels, lut, rng, out, _stream()))
+
+
+# ---- feature pictures (include/stego_pca.h; stego_amd.feature_pca wraps them)
+def pca_desc(B, C, h, w, H=1, W=1, joint=False, n_iter=PCA_DEFAULT_ITER, resize=PCA_BILINEAR, scale=PCA_UNIT, out_strides=(0, 0)):
+    return StegoPcaDesc(int(B), int(C), int(h), int(w), int(H), int(W), PCA_JOINT if joint is True else PCA_PER_IMAGE if joint is False
+                        else int(joint), int(n_iter), int(resize), int(scale), int(out_strides[0]), int(out_strides[1]))
+
+
+def pca_workspace_bytes(desc):
+    """stego_pca_workspace_bytes (host only); 0 for an invalid descriptor."""
+    return int(load().stego_pca_workspace_bytes(byref(desc)))
+
+
+def pca_fit_raw(desc, fmap, mean, cov, basis, stats, workspace, workspace_bytes, stream=None):
+    """stego_pca_fit with every argument given: `fmap` is a StegoMap (or None), the rest raw addresses or tensors -> the return code,
+    unchecked."""
+    return int(load().stego_pca_fit(_desc_ref(desc), _ref(fmap), _addr(mean), _addr(cov), _addr(basis), _addr(stats), _addr(workspace),
+                                    int(workspace_bytes), stream if stream is not None else None))
+
+
+def pca_scores_raw(desc, fmap, mean, basis, scores, rng, workspace, workspace_bytes, stream=None):
+    """stego_pca_scores with every argument given -> the return code, unchecked."""
+    return int(load().stego_pca_scores(_desc_ref(desc), _ref(fmap), _addr(mean), _addr(basis), _addr(scores), _addr(rng),
+                                       _addr(workspace), int(workspace_bytes), stream if stream is not None else None))
+
+
+def pca_paint_raw(desc, scores, rng, out, stream=None):
+    """stego_pca_paint with every argument given -> the return code, unchecked."""
+    return int(load().stego_pca_paint(_desc_ref(desc), _addr(scores), _addr(rng), _addr(out), stream if stream is not None else None))
+
+
+def _pca_workspace(desc, dev):
+    need = pca_workspace_bytes(desc)
+    if need == 0:
+        _check(pca_paint_raw(desc, None, None, None))          # raises with the descriptor's own code
+    return _empty_bytes(need, dev), need
+
+
+def pca_fit(desc, fmap):
+    """Stages (a) - (c) of include/stego_pca.h on torch's current stream -> (mean [G, C], cov float64 [G, C, C], basis [G, 3, C],
+    stats [G, 3, 3]), nothing synchronised."""
+    _require_dev(fmap)
+    dev = fmap.device
+    G, C = (1 if desc.group == PCA_JOINT else desc.B), desc.C
+    ws, need = _pca_workspace(desc, dev)
+    mean = torch.empty((G, C), dtype=torch.float32, device=dev)
+    cov = torch.empty((G, C, C), dtype=torch.float64, device=dev)
+    basis = torch.empty((G, 3, C), dtype=torch.float32, device=dev)
+    stats = torch.empty((G, 3, 3), dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        _check(pca_fit_raw(desc, _map(fmap), mean, cov, basis, stats, ws, need, _stream()))
+    return mean, cov, basis, stats
+
+
+def pca_scores(desc, fmap, mean, basis):
+    """Stage (d) -> (scores [B, h, w, 3], range [G, 3, 2])."""
+    _require_dev(fmap, mean, basis)
+    dev = fmap.device
+    G = 1 if desc.group == PCA_JOINT else desc.B
+    ws, need = _pca_workspace(desc, dev)
+    scores = torch.empty((desc.B, desc.h, desc.w, 3), dtype=torch.float32, device=dev)
+    rng = torch.empty((G, 3, 2), dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        _check(pca_scores_raw(desc, _map(fmap), mean, basis, scores, rng, ws, need, _stream()))
+    return scores, rng
+
+
+def pca_paint(desc, scores, rng, out):
+    """Stage (e): `out` is a uint8 tensor whose first element is the target's base (the descriptor holds its strides)."""
+    _require_dev(scores, rng, out)
+    with _on_device(out.device):
+        _check(pca_paint_raw(desc, scores, rng, out, _stream()))
 
 
 # ---- device-side confusion matrices (include/stego_confusion.h; stego_amd.metrics wraps them for the trainer and evaluate())

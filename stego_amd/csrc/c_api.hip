@@ -22,6 +22,7 @@
 #include "../../include/stego_rec.h"
 #include "../../include/stego_render.h"
 #include "../../include/stego_stats.h"
+#include "../../include/stego_pca.h"
 #include "corr_wide.h"
 #include "launchers.h"
 
@@ -387,6 +388,10 @@ const char* stego_error_string(int code)
         case STEGO_ERR_STATS_COUNT: return "step stats: n_tensors outside [1, 4], n_scalars outside [0, 16], or a count outside [0, 2^31) (include/stego_stats.h)";
         case STEGO_ERR_STATS_RING: return "step stats: ring_slots outside [1, 65536]";
         case STEGO_ERR_STATS_FLAGS: return "step stats: with_hist neither 0 nor 1";
+        case STEGO_ERR_PCA_DIM: return "pca: C outside [3, 768] (include/stego_pca.h)";
+        case STEGO_ERR_PCA_SIZE: return "pca: B outside [1, 65535], h or w outside [1, 4096], more than 2^28 tokens, fewer than 4 tokens in a group, or H or W outside [1, 32768]";
+        case STEGO_ERR_PCA_ITER: return "pca: n_iter outside [1, 256]";
+        case STEGO_ERR_PCA_MODE: return "pca: group, resize or scale is none of its two values";
         case STEGO_ERR_CRF_RANGE: return "dense CRF: a lattice coordinate would leave the packed key (image too large for its standard deviations)";
         default: return code >= STEGO_ERR_HIP ? "HIP runtime error (code - 1000 = hipError_t)" : "unknown error";
     }

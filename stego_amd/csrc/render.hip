@@ -20,6 +20,7 @@
 
 #include "../../include/stego_render.h"
 #include "host_util.h"
+#include "rgb_rows.h"
 
 using namespace stego;
 
@@ -30,15 +31,7 @@ using namespace stego;
 
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));       // 16 bytes of a lane
-
 constexpr int TPB = 256;
-constexpr int ROWS = 16;                 // rows of a workgroup
-constexpr int CHUNK = 768;               // bytes of a row per workgroup: 48 pieces of 16 bytes, 256 pixels
-constexpr int PIECES = CHUNK / 16;
-constexpr int CPIX = CHUNK / 3;          // 256
-constexpr int PIX_BACK = 5;              // a chunk's first pixel is at most (15 + 2) / 3 pixels in front of 256 c
-constexpr int PIX_SPAN = CPIX + PIX_BACK;
 constexpr int PIX_BATCH = 4;             // pixels of a lane whose image values are in flight together
 constexpr int TILE_BACK = 16;            // the label tile starts 16 columns in front of 256 c: a 16-byte boundary for every label type
 constexpr int TILE_W = CPIX + 2 * TILE_BACK;
@@ -72,12 +65,6 @@ __device__ __forceinline__ float unnormalise(float x, float s, float m)
 {
     const float scaled = x * s;
     return scaled + m;
-}
-
-__device__ __forceinline__ uint32_t to_level(float f)
-{
-    const float p = f * 255.f;
-    return (uint32_t)(int)fminf(fmaxf(p, 0.f), 255.f);       // fmaxf(NaN, 0) = 0; the conversion truncates
 }
 
 template <class LT>
@@ -157,8 +144,7 @@ __global__ __launch_bounds__(TPB) void render_kernel(const RenderParams p)
             live[u] = false;
             val[u][0] = val[u][1] = val[u][2] = 0.f;
             if (i >= N_PIX || y >= p.H || x < 0 || x >= p.W) continue;
-            const int a = (int)(reinterpret_cast<uintptr_t>(out_b + (int64_t)y * p.osh) & 15);
-            const int at = 3 * x + a - c * CHUNK;                        // the pixel's first byte in the chunk
+            const int at = pixel_place(out_b + (int64_t)y * p.osh, x, c);
             if (at + 2 < 0 || at >= CHUNK) continue;
             live[u] = true;
             if (has_img) {
@@ -172,8 +158,7 @@ __global__ __launch_bounds__(TPB) void render_kernel(const RenderParams p)
             if (!live[u]) continue;
             const int i = base + u * TPB;
             const int r = i / PIX_SPAN, x = pix_x0 + (i - r * PIX_SPAN), y = y0 + r;
-            const int a = (int)(reinterpret_cast<uintptr_t>(out_b + (int64_t)y * p.osh) & 15);
-            const int at = 3 * x + a - c * CHUNK;
+            const int at = pixel_place(out_b + (int64_t)y * p.osh, x, c);
             uint32_t rgb = 0;
             if (has_lab) {
                 const ST* row = tile + r * TILE_W + (x - tile_x0);
@@ -198,34 +183,11 @@ __global__ __launch_bounds__(TPB) void render_kernel(const RenderParams p)
                     px |= to_level(v) << (8 * ch);
                 }
             }
-            uint8_t* dst = stage + r * CHUNK;
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                if (at + k >= 0 && at + k < CHUNK) dst[at + k] = (uint8_t)(px >> (8 * k));
+            put_pixel(stage + r * CHUNK, at, px);
         }
     }
     __syncthreads();
-
-    const int row_bytes = 3 * p.W;
-    for (int i = t; i < ROWS * PIECES; i += TPB) {
-        const int r = i / PIECES, s = i - r * PIECES, y = y0 + r;
-        if (y >= p.H) continue;
-        uint8_t* const row = out_b + (int64_t)y * p.osh;
-        const int a = (int)(reinterpret_cast<uintptr_t>(row) & 15);
-        const int q = c * CHUNK + 16 * s;                                // the piece, in bytes from the row's aligned address
-        const int from = q > a ? q : a, to = q + 16 < a + row_bytes ? q + 16 : a + row_bytes;
-        if (from >= to) continue;
-        uint8_t* const g = row - a + q;                                  // 16-byte aligned
-        const uint8_t* const l = stage + r * CHUNK + 16 * s;
-        if (to - from == 16) {
-            *reinterpret_cast<u32x4*>(g) = *reinterpret_cast<const u32x4*>(l);
-        } else {
-            for (int k = from - q; k < to - q; ++k) {
-                g[k] = l[k];
-                asm volatile("" ::: "memory");            // byte stores as written: no wide copy of an unaligned run
-            }
-        }
-    }
+    store_rows<TPB>(out_b, p.osh, stage, c, y0, p.H, p.W);
 }
 
 __device__ __forceinline__ void wave_min_max(float& lo, float& hi)

@@ -17,6 +17,13 @@ before it is copied to the host: `linear_color/` and `cluster_color/` are the la
 `overlay/` is the image, at weight 1 - `overlay_alpha`, under the cluster colours with the segment boundaries drawn.  The clusters
 are coloured by class through the checkpoint's cluster -> class assignment when it stores one (`model.cluster_to_class`), else by
 their own index.  `linear/` and `cluster/` and the returned list are the same with and without it.
+
+With `save_pca=True` every image also gets the two three-principal-component pictures of stego_amd.feature_pca (csrc/feature_pca.hip),
+at the size of its label maps: `pca_feats/` shows the backbone features, every component brought to its own range, and `pca_code/`
+the segmentation code, L2-normalised per token, as (p + 1) / 2 - the picture of the reference's src/train_crf.py:145-150.  One model
+is fitted per batch, so the images of a batch share their colours.  Under `full_res` an image is a set of overlapping windows, each
+with a low-resolution map of its own, and there is no single map per image short of running the backbone again: `save_pca` writes
+nothing there.
 """
 import os
 import sys
@@ -121,6 +128,22 @@ def my_app(cfg):
             for j, name in enumerate(names):
                 Image.fromarray(rgb[j]).save(join(out, sub, prediction_name(name)))         # [H, W, 3] uint8: mode "RGB"
 
+    save_pca = getattr(cfg, "save_pca", False) and not getattr(cfg, "full_res", False)
+    if save_pca:
+        from .feature_pca import feature_pictures
+        for sub in ("pca_feats", "pca_code"):
+            os.makedirs(join(out, sub), exist_ok=True)
+
+    def save_pcas(names, maps, size):
+        """Both feature pictures of every image of a batch: one joint fit per map, painted at the label maps' size."""
+        code = torch.nn.functional.normalize(maps["code"].detach().float(), dim=1)
+        pictures = (("pca_feats", feature_pictures(maps["feats"].detach().float(), size=size, joint=True, scale="range")),
+                    ("pca_code", feature_pictures(code, size=size, joint=True, scale="unit")))
+        for sub, rgb in pictures:
+            rgb = rgb.cpu().numpy()
+            for j, name in enumerate(names):
+                Image.fromarray(rgb[j]).save(join(out, sub, prediction_name(name)))
+
     if getattr(cfg, "full_res", False):
         dataset = UnlabeledImageFolder(cfg.image_dir, full_image_transform(cfg.res))
         loader = torch.utils.data.DataLoader(dataset, 1, shuffle=False, num_workers=cfg.num_workers, collate_fn=first)
@@ -145,9 +168,12 @@ def my_app(cfg):
         if imgs is None:
             continue
         imgs = imgs.to(dev)
-        linear, cluster = segment(model, imgs, run_crf=run_crf)
+        maps = {} if save_pca else None
+        linear, cluster = segment(model, imgs, run_crf=run_crf, maps=maps)
         if save_color:
             save_colors(names, imgs, linear, cluster)
+        if save_pca:
+            save_pcas(names, maps, tuple(linear.shape[-2:]))
         linear, cluster = linear.cpu().numpy(), cluster.cpu().numpy()
         for j, name in enumerate(names):
             save(name, linear[j], cluster[j])

@@ -212,6 +212,12 @@ def colorize(labels, cmap, mapping=None, image=None, alpha=0.5, edges=False, out
 
 
 def _panel_shape(spec):
+    if "features" in spec:
+        t = spec["features"]
+        if t.dim() != 4:
+            raise ValueError("features: expected [B, C, h, w], got %s" % (tuple(t.shape),))
+        H, W = spec["size"] if spec.get("size") is not None else t.shape[-2:]
+        return int(t.shape[0]), int(H), int(W), t.device
     t = spec["labels"] if "labels" in spec else spec["image"]
     dims = 2 if "labels" in spec else 3
     t, _ = _batched(t, dims, "panel")
@@ -220,8 +226,9 @@ def _panel_shape(spec):
 
 def comparison_sheet(rows, pad=4, background=(255, 255, 255)):
     """One uint8 [SH, SW, 3] sheet of panels.  `rows` is a list of rows; a row is the keyword arguments of one call as a dict:
-    ``{"image": img, "rescale": True}`` for image_u8, or ``{"labels": l, "cmap": c, ...}`` for colorize.  The tensors of a row are
-    batched ([B, ...]; an unbatched one is a row of one panel): its B panels stand side by side, `pad` pixels of `background` around
+    ``{"image": img, "rescale": True}`` for image_u8, ``{"labels": l, "cmap": c, ...}`` for colorize, or ``{"features": maps, "size":
+    (H, W), "joint": ..., "scale": ..., "resize": ...}`` for feature_pca.feature_pictures (a [B, C, h, w] map; size defaults to (h, w)).
+    The tensors of a row are batched ([B, ...]; an unbatched image or label map is a row of one panel): its B panels stand side by side, `pad` pixels of `background` around
     and between them, the rows below one another.  The sheet is allocated once and every row renders straight into its place
     through the strided target: no per-panel tensor, no copy."""
     if not rows:
@@ -237,7 +244,10 @@ def comparison_sheet(rows, pad=4, background=(255, 255, 255)):
     for spec, (B, H, W, _) in zip(rows, shapes):
         view = torch.as_strided(sheet, (B, H, W, 3), ((W + pad) * 3, SW * 3, 3, 1), (y * SW + pad) * 3)
         spec = dict(spec)
-        if "labels" in spec:
+        if "features" in spec:
+            from .feature_pca import feature_pictures
+            feature_pictures(spec.pop("features"), out=view, **spec)
+        elif "labels" in spec:
             labels, _ = _batched(spec.pop("labels"), 2, "labels")
             colorize(labels, spec.pop("cmap"), out=view, **spec)
         else:

@@ -40,10 +40,12 @@ def probe_head(model, code, code_flip, size, linear="log_probs", cluster="log_pr
                                linear, cluster, alpha)
 
 
-def segment(model, img, run_crf=True, flip=True, res=None):
+def segment(model, img, run_crf=True, flip=True, res=None, maps=None):
     """Normalised images [B, 3, H, W] -> (linear_preds, cluster_preds), int64 [B, res, res] (default: the images' H, W): the backbone
     on the images and on their mirror images, the fused probe head, then the dense CRF on both probes' probabilities (run_crf) and
-    the argmax.  The CRF runs at the image's resolution, so `res` must equal it when run_crf is set."""
+    the argmax.  The CRF runs at the image's resolution, so `res` must equal it when run_crf is set.
+    maps: a dict that receives what the backbone returned for the unflipped images, "feats" [B, C, h, w] and "code" [B, K, h, w]
+    (stego_amd.feature_pca draws them); nothing else changes."""
     _device_tensor(img, "img")
     if img.dim() != 4 or img.shape[1] != 3:
         raise ValueError("img: expected [B, 3, H, W], got %s" % (tuple(img.shape),))
@@ -51,7 +53,9 @@ def segment(model, img, run_crf=True, flip=True, res=None):
     if run_crf and size != tuple(img.shape[-2:]):
         raise ValueError("segment: the CRF runs at the image's resolution %s, res = %s" % (tuple(img.shape[-2:]), size))
     with torch.no_grad():
-        _, code1 = model.net(img)
+        feats, code1 = model.net(img)
+        if maps is not None:
+            maps["feats"], maps["code"] = feats, code1
         code2 = model.net(img.flip(dims=[3]))[1] if flip else None
         kind = "probs" if run_crf else "argmax"
         lin, clu = probe_head(model, code1, code2, size, linear=kind, cluster=kind)
