@@ -14,7 +14,8 @@
  * segmentation head of this library use), in STEGO_VIT_F16 as plain fp16 operands (2 - 3 x faster, error at the level of
  * torch's fp16 autocast).  Measured deviations from the fp32 / fp64 torch model: DESIGN.md 4.9 / tests/test_vit_native.py.
  * The attention maps and the qkv tensor the reference materialises at every block (:232-236) are never built; the keys of the last
- * block, the reference's feature type "KK", come from stego_vit_forward_keys.
+ * block, the reference's feature type "KK", come from stego_vit_forward_keys, and the one row of the last block's attention maps that
+ * outlines the foreground - the class token's - from stego_vit_forward_attn; stego_attn_salience makes a mask of it.
  *
  * Conventions as in stego_corr.h: device pointers, nothing allocated / freed / synchronised, work enqueued on
  * `stream`, return STEGO_OK or an error code.
@@ -80,6 +81,34 @@ int stego_vit_forward(const StegoVitDesc* d, const void* packed, const float* im
  * accumulators directly: F16X3 keys are fp32 class, F16 keys carry the operand rounding only. */
 int stego_vit_forward_keys(const StegoVitDesc* d, const void* packed, const float* img, float* keys_out, void* workspace,
                            size_t workspace_bytes, stego_stream_t stream);
+
+/* tokens_out exactly as stego_vit_forward (same launches, same bits), and in addition
+ * attn_out: OUT fp32 [B, heads, 1 + hw]: softmax_t(q_cls . k_t / 8) of block depth-1,
+ * i.e. attn[:, :, 0, :] of vision_transformer.py:83-85 / get_last_selfattention (:239-246).
+ * Column 0 is the class token's own weight; each row sums to 1 over the 1 + hw real tokens.
+ * One more launch after those of stego_vit_forward: a read-only pass over the Q and K the last block's QKV GEMM left in the workspace
+ * (one workgroup per image and head; F16X3: q = hi + lo and k = hi + lo in fp32 FMAs, F16: the fp16 operands; fp32 statistics).  The
+ * entry point is combined on purpose: the workspace holds that Q and K only right after a stego_vit_forward of the same batch
+ * (stego_vit_forward_keys stops before the last QKV GEMM).  Argument checks as stego_vit_forward, attn_out: non-NULL, 4-byte aligned. */
+int stego_vit_forward_attn(const StegoVitDesc* d, const void* packed, const float* img, float* tokens_out, float* attn_out, void* workspace,
+                           size_t workspace_bytes, stego_stream_t stream);
+
+/* An attention salience mask per image: the smallest set of strongest patches that holds `keep` of the class token's attention mass.
+ * attn: [B, heads, 1 + h*w] as above.  Per image, in fp64 from the fp32 inputs:
+ *   m_i     = sum over heads (head order) of attn[b, hd, 1 + i]          i = 0 .. h*w-1 (class column left out)
+ *   T       = sum_i m_i (index order)
+ *   ahead_i = sum of m_j over the patches that come before i in the order (m descending, index ascending on ties)
+ *   kept_i  = ahead_i < (double)keep * T        (the smallest set of strongest patches holding >= keep of the mass)
+ * soft: OUT fp32 [B, h, w] = m_i / T, may be NULL.
+ * mask: OUT uint8 [B, h*patch, w*patch], kept_i replicated over its patch (0 / 1), may be NULL; 16-byte aligned.
+ * 0 < keep <= 1.
+ * The kernel (a workgroup per image and slice of patch rows) needs no sort: ahead_i is accumulated in increasing j over the j with
+ * m_j > m_i, or equal and j < i; T by a tree.  Both differ from the sums in the stated order by fp64 rounding only (1e-16 relative), so kept_i is the stated one
+ * wherever |ahead_i - keep * T| / T is above that.
+ * Errors, all before the first HIP call: STEGO_ERR_NULL (attn), STEGO_ERR_SHAPE (B, heads, h, w <= 0; keep outside (0, 1]),
+ * STEGO_ERR_UNSUPPORTED (patch not 8 or 16; h*w > 4096 - 512 x 512 pixels at patch 8), STEGO_ERR_ALIGN.                                 */
+int stego_attn_salience(const float* attn, int32_t B, int32_t heads, int32_t h, int32_t w, int32_t patch, float keep,
+                        float* soft, uint8_t* mask, stego_stream_t stream);
 
 #ifdef __cplusplus
 }

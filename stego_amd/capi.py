@@ -275,6 +275,8 @@ SIGNATURES = {
     "stego_vit_pack_weights": (c_int32, [_V, POINTER(ctypes.c_void_p), c_int32, _P, c_size_t, _P]),
     "stego_vit_forward": (c_int32, [_V, _P, _P, _P, _P, c_size_t, _P]),
     "stego_vit_forward_keys": (c_int32, [_V, _P, _P, _P, _P, c_size_t, _P]),
+    "stego_vit_forward_attn": (c_int32, [_V, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "stego_attn_salience": (c_int32, [_P] + [c_int32] * 5 + [c_float, _P, _P, _P]),
     "stego_head_fwd_workspace_bytes": (c_size_t, [_H]),
     "stego_head_bwd_workspace_bytes": (c_size_t, [_H]),
     "stego_head_fwd": (c_int32, [_H] + [_P] * 10 + [_P] * 3 + [_P, c_size_t, _P]),

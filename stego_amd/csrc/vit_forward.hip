@@ -20,6 +20,7 @@
 #include "../../include/stego_vit.h"
 #include "corr_common.h"
 #include "host_util.h"
+#include "vit_cls_attn.h"
 
 namespace stego {
 namespace vit {
@@ -844,6 +845,25 @@ int stego_vit_forward_keys(const StegoVitDesc* d, const void* packed, const floa
                            size_t workspace_bytes, stego_stream_t stream)
 {
     return vit_forward_impl(d, packed, img, keys_out, workspace, workspace_bytes, stream, true);
+}
+
+// stego_vit_forward, then the class token's attention row of block depth-1 from the Q and K that block's QKV GEMM left in the workspace
+// (csrc/vit_cls_attn.hip): the launches of stego_vit_forward, unchanged, and one more
+int stego_vit_forward_attn(const StegoVitDesc* d, const void* packed, const float* img, float* tokens_out, float* attn_out, void* workspace,
+                           size_t workspace_bytes, stego_stream_t stream)
+{
+    const int rc = check_desc(d);
+    if (rc != STEGO_OK) return rc;
+    if (!packed || !img || !tokens_out || !attn_out || !workspace) return STEGO_ERR_NULL;
+    if (reinterpret_cast<uintptr_t>(attn_out) & 3) return STEGO_ERR_ALIGN;
+    const int rf = vit_forward_impl(d, packed, img, tokens_out, workspace, workspace_bytes, stream, false);
+    if (rf != STEGO_OK) return rf;
+    const Layout L = make_layout(*d);
+    const Workspace w = make_workspace(*d, L);
+    unsigned char* ws = static_cast<unsigned char*>(workspace);
+    VIT_TRY(launch_cls_attn(reinterpret_cast<const half_t*>(ws + w.q), reinterpret_cast<const half_t*>(ws + w.k), w.plane, L.ntok, w.ntok_pad,
+                            d->heads, d->B, d->precision == STEGO_VIT_F16X3, attn_out, static_cast<hipStream_t>(stream)));
+    return STEGO_OK;
 }
 
 }  // extern "C"

@@ -24,6 +24,10 @@ the segmentation code, L2-normalised per token, as (p + 1) / 2 - the picture of 
 is fitted per batch, so the images of a batch share their colours.  Under `full_res` an image is a set of overlapping windows, each
 with a low-resolution map of its own, and there is no single map per image short of running the backbone again: `save_pca` writes
 nothing there.
+
+With `save_salience=True` every image also gets its attention salience mask (stego_amd.salience: the strongest patches holding
+`salience_keep` of the class token's attention in the backbone's last block) as `salience/NAME.png` (0 / 255) and, beside the image,
+as `salience_sheet/NAME.png`.  It costs one more backbone pass per batch and, like `save_pca`, writes nothing under `full_res`.
 """
 import os
 import sys
@@ -144,6 +148,27 @@ def my_app(cfg):
             for j, name in enumerate(names):
                 Image.fromarray(rgb[j]).save(join(out, sub, prediction_name(name)))
 
+    save_salience = getattr(cfg, "save_salience", False) and not getattr(cfg, "full_res", False)
+    if save_salience:
+        from .render import IMAGENET_MEAN, IMAGENET_STD, colorize, image_u8
+        from .salience import image_salience
+        for sub in ("salience", "salience_sheet"):
+            os.makedirs(join(out, sub), exist_ok=True)
+        salience_keep = float(getattr(cfg, "salience_keep", 0.6))
+
+    def save_saliences(names, imgs):
+        """The attention salience mask of every image of a batch (stego_amd.salience) as a 0 / 255 PNG, and the image beside it."""
+        mask = image_salience(model.net, imgs, keep=salience_keep)[1]
+        N, H, W = mask.shape
+        pad = 4
+        sheet = torch.full((N, H, 2 * W + pad, 3), 255, dtype=torch.uint8, device=mask.device)
+        image_u8(imgs, rescale=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=sheet[:, :, :W])
+        colorize(mask, np.array([[0, 0, 0], [255, 255, 255]], dtype=np.uint8), out=sheet[:, :, W + pad:])
+        mask, sheet = (mask * 255).cpu().numpy(), sheet.cpu().numpy()
+        for j, name in enumerate(names):
+            Image.fromarray(mask[j]).save(join(out, "salience", prediction_name(name)))
+            Image.fromarray(sheet[j]).save(join(out, "salience_sheet", prediction_name(name)))
+
     if getattr(cfg, "full_res", False):
         dataset = UnlabeledImageFolder(cfg.image_dir, full_image_transform(cfg.res))
         loader = torch.utils.data.DataLoader(dataset, 1, shuffle=False, num_workers=cfg.num_workers, collate_fn=first)
@@ -174,6 +199,8 @@ def my_app(cfg):
             save_colors(names, imgs, linear, cluster)
         if save_pca:
             save_pcas(names, maps, tuple(linear.shape[-2:]))
+        if save_salience:
+            save_saliences(names, imgs)
         linear, cluster = linear.cpu().numpy(), cluster.cpu().numpy()
         for j, name in enumerate(names):
             save(name, linear[j], cluster[j])

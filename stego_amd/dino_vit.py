@@ -144,6 +144,10 @@ class VisionTransformer(nn.Module):
                 qkvs.append(qkv)
         return feats, attns, qkvs
 
+    def get_last_selfattention(self, x):
+        """The attention maps [B, heads, N, N] of the last block (reference :239-246)."""
+        return self.get_intermediate_feat(x, n=1, need_attn=True)[1][0]
+
     def get_intermediate_layers(self, x, n=1):
         return self.get_intermediate_feat(x, n)[0]
 

@@ -238,8 +238,9 @@ class DinoFeaturizer(nn.Module):
             return None
         return self._native
 
-    def _tokens(self, img, n):
-        """feat[0] (and qkv[0]) of get_intermediate_feat (modules.py:88-89).  On a HIP device the frozen backbone runs on the
+    def _tokens(self, img, n, need_attn=False):
+        """feat[0] (and qkv[0]) of get_intermediate_feat (modules.py:88-89); with need_attn a third entry, the class token's attention row
+        of the last block [B, heads, 1 + hw], from the same pass.  On a HIP device the frozen backbone runs on the
         hand-written kernels of include/stego_vit.h - DEFAULT (cfg.native_backbone, True unless set False) in precision
         cfg.backbone_precision = "f16x3": split-fp16 operands with three MFMAs per product, fp32 accumulation, statistics and
         residual stream; its error against the fp64 model is at or below the fp32 torch model's own (tests/test_vit_native.py:
@@ -250,9 +251,14 @@ class DinoFeaturizer(nn.Module):
         native = self._native_backbone(img, n) if self.feat_type == "feat" else None
         if native is not None:
             self.backbone_path = "native"
+            if need_attn:                                   # the same launches and one more: the tokens are bit for bit forward_tokens'
+                tokens, attn = native.forward_tokens_attn(img)
+                return tokens, None, attn
             return native.forward_tokens(img), None
         self.backbone_path = "torch"
-        feat, _, qkv = self.model.get_intermediate_feat(img, n=n)
+        feat, attns, qkv = self.model.get_intermediate_feat(img, n=n, need_attn=need_attn)
+        if need_attn:                                       # (the torch module then forms attn @ v itself instead of the fused attention)
+            return feat[0], qkv[0], attns[-1][:, :, 0, :]
         return feat[0], qkv[0]
 
     def _keys(self, img):
@@ -261,13 +267,33 @@ class DinoFeaturizer(nn.Module):
         self.backbone_path = "native"
         return self._native.forward_keys(img)
 
+    def class_attention(self, img):
+        """The class token's attention over the tokens in the last block, [B, heads, 1 + hw] (column 0: its own weight; rows sum to 1):
+        the map that outlines the foreground in a DINO ViT.  On the native backbone one launch after the token forward
+        (NativeViT.forward_tokens_attn); otherwise row 0 of the torch module's attention maps."""
+        if self.model.training:
+            self.model.eval()
+        with torch.no_grad():
+            native = self._native_backbone(img, 1)
+            if native is not None:
+                self.backbone_path = "native"
+                return native.forward_tokens_attn(img)[1]
+            self.backbone_path = "torch"
+            return self.model.get_last_selfattention(img)[:, :, 0, :]
+
     def enable_token_cache(self, n_items, img_hw, device, dtype=torch.float16):
         """Keep the backbone tokens of dataset items 0..n_items-1 in device memory (see TokenCache)."""
         ntok = 1 + (img_hw[0] // self.patch_size) * (img_hw[1] // self.patch_size)
         self.token_cache = TokenCache(n_items, ntok, self.n_feats, device, dtype)
         return self.token_cache
 
-    def forward(self, img, n=1, return_class_feat=False, cache_index=None):
+    def forward(self, img, n=1, return_class_feat=False, cache_index=None, return_attention=False):
+        """(feats, code); with return_attention (feats, code, attn), attn = class_attention(img) from the same backbone pass (feat_type 'KK'
+        on the native backbone: a second pass, the keys' forward stops before the last block's QKV GEMM).  Cached tokens carry no
+        attention: with a cache_index it raises."""
+        if return_attention and cache_index is not None:
+            raise ValueError("DinoFeaturizer: return_attention with a cache_index - cached tokens carry no attention")
+        attn = None
         if self.model.training:              # (modules.py:80 calls eval() on every forward: ~130 modules walked in Python, 0.45 ms per call)
             self.model.eval()
         with torch.no_grad():
@@ -282,9 +308,13 @@ class DinoFeaturizer(nn.Module):
             native_keys = native_kk is not None and not return_class_feat
             if native_keys:
                 feat, qkv = (self.token_cache.fetch(cache_index, img, self._keys) if cached else self._keys(img)), None
+                if return_attention:
+                    attn = native_kk.forward_tokens_attn(img)[1]
             elif native_kk is not None:
                 self.backbone_path = "native"
                 feat, qkv = native_kk.forward_tokens(img), None
+            elif return_attention:
+                feat, qkv, attn = self._tokens(img, n, need_attn=True)
             elif cached and self.feat_type == "feat":
                 feat, qkv = self.token_cache.fetch(cache_index, img, lambda sub: self._tokens(sub, 1)[0]), None
             else:
@@ -307,11 +337,13 @@ class DinoFeaturizer(nn.Module):
                 if cache_index is not None and self.token_cache is not None and self.token_cache.last is not None and \
                         self.token_cache.last[0] is feat:
                     amax = self.token_cache.last[1]
-                return self._head_native(image_feat, amax)
+                out = self._head_native(image_feat, amax)
+                return out + (attn,) if return_attention else out
             code = self._head(image_feat)
         else:
             code = image_feat
-        return (self.dropout(image_feat) if self.cfg.dropout else image_feat), code
+        out = (self.dropout(image_feat) if self.cfg.dropout else image_feat), code
+        return out + (attn,) if return_attention else out
 
     def _native_head_ok(self, image_feat):
         """The hand-written head kernels (include/stego_head.h) take channels-last fp32 token maps on a HIP device; cfg.native_head

@@ -28,6 +28,7 @@ from .featurizers import ClusterLookup, ContrastiveCRFLoss, DinoFeaturizer, Feat
 from .modules import ContrastiveCorrelationLoss, norm, sample
 from .probe_train import probe_losses, torch_probe_losses
 from .rec_loss import rec_loss as native_rec_loss
+from .salience import attention_salience
 from .metrics import DeviceUnsupervisedMetrics, probe_confusion
 from .utils import UnsupervisedMetrics, one_hot_feats, prep_args, resize
 
@@ -125,6 +126,16 @@ class LitUnsupervisedSegmenter(nn.Module):
                     warnings.warn("cfg.dim=%d: code dimensions above %d run on the single-launch forward only, and %s: this configuration "
                                   "runs on ContrastiveCorrelationLoss.generic_forward: same results, several times slower"
                                   % (dim, MAX_CODE_DIM_ANY_PATH, "; ".join(why)))
+        # cfg.salience_source: where cfg.use_salience gets its foreground masks - "mask" (batch["mask"], the default) or "attention" (the class
+        # token's attention of the backbone, stego_amd.salience: a folder without labels has no other)
+        source = getattr(cfg, "salience_source", "mask")
+        if source not in ("mask", "attention"):
+            raise ValueError("cfg.salience_source = %r, expected 'mask' or 'attention'" % (source,))
+        if source == "attention" and getattr(cfg, "cache_backbone_tokens", False):
+            raise ValueError("cfg.salience_source = 'attention' needs the backbone's pass over every batch: cached tokens carry no attention "
+                             "(cfg.cache_backbone_tokens must be False)")
+        if source == "attention" and cfg.use_salience and not hasattr(self.net, "class_attention"):
+            raise ValueError("cfg.salience_source = 'attention' needs the DINO featurizer (cfg.arch = 'dino')")
         for p in self.contrastive_corr_loss_fn.parameters():
             p.requires_grad = False
         self.automatic_optimization = False
@@ -282,9 +293,15 @@ class LitUnsupervisedSegmenter(nn.Module):
         # cfg.cache_backbone_tokens: img / img_pos of a dataset index are the same pixels every epoch -> their frozen-backbone
         # tokens come from the HBM table after the first epoch (featurizers.TokenCache)
         caching = getattr(cfg, "cache_backbone_tokens", False) and getattr(self.net, "token_cache", None) is not None
-        feats, code = self.net(img, cache_index=batch["ind"]) if caching else self.net(img)
-        if cfg.correspondence_weight > 0:
-            feats_pos, code_pos = self.net(img_pos, cache_index=batch["ind_pos"]) if caching else self.net(img_pos)
+        # cfg.salience_source "attention": the class token's attention comes out of the two backbone passes the step makes anyway
+        attn_salience = bool(cfg.use_salience) and getattr(cfg, "salience_source", "mask") == "attention" and cfg.correspondence_weight > 0
+        if attn_salience:
+            feats, code, attn = self.net(img, return_attention=True)
+            feats_pos, code_pos, attn_pos = self.net(img_pos, return_attention=True)
+        else:
+            feats, code = self.net(img, cache_index=batch["ind"]) if caching else self.net(img)
+            if cfg.correspondence_weight > 0:
+                feats_pos, code_pos = self.net(img_pos, cache_index=batch["ind_pos"]) if caching else self.net(img_pos)
         log_args = dict(sync_dist=False, rank_zero_only=True)
         if cfg.use_true_labels:
             signal = one_hot_feats(label + 1, self.n_classes + 1)
@@ -293,7 +310,16 @@ class LitUnsupervisedSegmenter(nn.Module):
             signal, signal_pos = feats, feats_pos
         loss = 0
         stats_cd = None
-        if cfg.use_salience:
+        if attn_salience:
+            # masks [B, H, W] uint8 at the image's resolution (include/stego_vit.h: stego_attn_salience), batch["mask"] is not read; the
+            # native draw takes them as they are, the torch draw gets floats as it does from the loader.  No host synchronisation.
+            keep, ps = float(getattr(cfg, "salience_keep", 0.6)), self.net.patch_size
+            hw = (img.shape[2] // ps, img.shape[3] // ps)
+            salience = attention_salience(attn, hw, ps, keep)[1]
+            salience_pos = attention_salience(attn_pos, hw, ps, keep)[1]
+            if not getattr(cfg, "native_salience", False):
+                salience, salience_pos = salience.float(), salience_pos.float()
+        elif cfg.use_salience and getattr(cfg, "salience_source", "mask") == "mask":
             salience = batch["mask"].to(torch.float32).squeeze(1)
             salience_pos = batch["mask_pos"].to(torch.float32).squeeze(1)
         else:

@@ -5,7 +5,8 @@ Host-side mirror of what ``DinoFeaturizer.forward`` needs from the reference's
 src/modules.py:88): the normalised tokens of the last block (``forward_tokens``, ``feat_type == "feat"``, the default of
 train_config.yml) or that block's attention keys (``forward_keys``, ``feat_type == "KK"``, src/modules.py:98-101).  The
 reference also returns the attention maps and the whole qkv tensor of the block; neither feature type looks at more than the
-K third, so this path does not build them - callers that want ``n > 1`` keep using the torch module.
+K third, so this path does not build them - callers that want ``n > 1`` keep using the torch module.  The one row of the last
+block's attention maps that outlines the foreground, the class token's, comes with the tokens from ``forward_tokens_attn``.
 
 Weights are packed once per (H, W) from a ``dino_vit.VisionTransformer`` (same parameter names as the DINO
 checkpoints); torch is used for device memory and for the bicubic ``interpolate_pos_encoding`` only.
@@ -102,7 +103,13 @@ class NativeViT:
         key map.  The last block stops after the K third of its QKV GEMM; same packed weights and workspace as forward_tokens."""
         return self._forward(img, "stego_vit_forward_keys")
 
-    def _forward(self, img, entry):
+    def forward_tokens_attn(self, img):
+        """img fp32 [B,3,H,W] on a HIP device -> (tokens, attn): tokens bit for bit those of forward_tokens, attn fp32 [B, heads, 1 + hw]
+        the class token's attention row of the last block (= get_last_selfattention(img)[:, :, 0, :]; column 0 its own weight).  One
+        launch more than forward_tokens, over the Q and K that forward leaves in the workspace; same packed weights, same workspace."""
+        return self._forward(img, "stego_vit_forward_attn", with_attn=True)
+
+    def _forward(self, img, entry, with_attn=False):
         capi._require_dev(img)
         if img.dtype != torch.float32 or img.dim() != 4 or img.shape[1] != 3:
             raise RuntimeError("stego_vit: expected a float32 [B,3,H,W] image batch, got %s %s" % (img.dtype, tuple(img.shape)))
@@ -123,7 +130,10 @@ class NativeViT:
             self._ws[dev] = ws
         ps = self.model.patch_embed.patch_size
         out = torch.empty(B, 1 + (H // ps) * (W // ps), self.model.embed_dim, dtype=torch.float32, device=dev)
+        outs = [out]
+        if with_attn:
+            outs.append(torch.empty(B, desc.heads, out.shape[1], dtype=torch.float32, device=dev))
         with torch.cuda.device(dev):
-            capi._check(getattr(lib, entry)(ctypes.byref(desc), blob.data_ptr(), img.data_ptr(), out.data_ptr(), ws.data_ptr(),
+            capi._check(getattr(lib, entry)(ctypes.byref(desc), blob.data_ptr(), img.data_ptr(), *[o.data_ptr() for o in outs], ws.data_ptr(),
                                             ws.numel(), capi._stream()))
-        return out
+        return tuple(outs) if with_attn else out
