@@ -262,6 +262,16 @@ PCA_SCALES = {"unit": PCA_UNIT, "range": PCA_RANGE}
 PCA_MIN_C, PCA_MAX_C, PCA_MAX_B, PCA_MAX_SIDE, PCA_MAX_TOKENS, PCA_MIN_TOKENS = 3, 768, 65535, 4096, 1 << 28, 4
 PCA_MAX_ITER, PCA_DEFAULT_ITER, PCA_FOLD = 256, 32, 1024
 
+
+class StegoKmeansDesc(Structure):
+    """include/stego_kmeans.h"""
+    _fields_ = [(n, c_int32) for n in ("B", "K", "h", "w", "n")]
+
+
+KMEANS_ERR_DIM, KMEANS_ERR_SIZE, KMEANS_ERR_DRAW = 180, 181, 182
+KMEANS_MAX_K, KMEANS_MAX_N, KMEANS_MAX_B, KMEANS_MAX_TOKENS = 128, 64, 65535, (1 << 31) - 1
+KMEANS_FOLD, KMEANS_TILE, KMEANS_MAX_WORKGROUPS = 1024, 128, 512
+
 # name -> (restype, argtypes); every symbol include/stego_corr.h declares
 _P = c_void_p
 _H = POINTER(StegoHeadDesc)
@@ -300,6 +310,10 @@ SIGNATURES = {
     "stego_pca_fit": (c_int32, [POINTER(StegoPcaDesc), _M, _P, _P, _P, _P, _P, c_size_t, _P]),
     "stego_pca_scores": (c_int32, [POINTER(StegoPcaDesc), _M, _P, _P, _P, _P, _P, c_size_t, _P]),
     "stego_pca_paint": (c_int32, [POINTER(StegoPcaDesc), _P, _P, _P, _P]),
+    "stego_kmeans_workspace_bytes": (c_size_t, [POINTER(StegoKmeansDesc)]),
+    "stego_kmeans_plan": (c_size_t, [POINTER(StegoKmeansDesc), POINTER(c_int32)]),
+    "stego_kmeans_step": (c_int32, [POINTER(StegoKmeansDesc), _M, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "stego_kmeans_seed": (c_int32, [POINTER(StegoKmeansDesc), _M, _P, _P, _P, _P, c_size_t, _P]),
     "stego_probe_confusion": (c_int32, [POINTER(StegoProbeConfusionDesc), _M, _M] + [_P] * 6 + [_P]),
     "stego_probe_confusion_plan": (c_size_t, [POINTER(StegoProbeConfusionDesc), POINTER(c_int32), POINTER(c_int32)]),
     "stego_confusion": (c_int32, [POINTER(StegoConfusionDesc), _P, _P, _P, _P]),
@@ -1551,6 +1565,87 @@ def pca_paint(desc, scores, rng, out):
     _require_dev(scores, rng, out)
     with _on_device(out.device):
         _check(pca_paint_raw(desc, scores, rng, out, _stream()))
+
+
+# ---- cluster refit (include/stego_kmeans.h; stego_amd.cluster_refit wraps them)
+def kmeans_desc(B, K, h, w, n):
+    return StegoKmeansDesc(int(B), int(K), int(h), int(w), int(n))
+
+
+def kmeans_workspace_bytes(desc):
+    """stego_kmeans_workspace_bytes (host only); 0 for an invalid descriptor."""
+    return int(load().stego_kmeans_workspace_bytes(byref(desc)))
+
+
+def kmeans_plan(desc):
+    """stego_kmeans_plan (host only) -> (LDS bytes of the main launch, its workgroups); zeros for an invalid descriptor."""
+    wgs = c_int32(-1)
+    lds = load().stego_kmeans_plan(byref(desc), byref(wgs))
+    return int(lds), int(wgs.value)
+
+
+def kmeans_step_raw(desc, codes, cin, cout, labels, counts, stats, workspace, workspace_bytes, stream=None):
+    """stego_kmeans_step with every argument given: `codes` is a StegoMap (or None), the rest raw addresses or tensors -> the return
+    code, unchecked."""
+    return int(load().stego_kmeans_step(_desc_ref(desc), _ref(codes), _addr(cin), _addr(cout), _addr(labels), _addr(counts), _addr(stats),
+                                        _addr(workspace), int(workspace_bytes), stream if stream is not None else None))
+
+
+def kmeans_seed_raw(desc, codes, u, centroids, picks, workspace, workspace_bytes, stream=None):
+    """stego_kmeans_seed with every argument given; `u` is a host address (a ctypes array of doubles), a raw address or None -> the
+    return code, unchecked."""
+    if isinstance(u, ctypes.Array):
+        u = ctypes.cast(u, c_void_p)
+    return int(load().stego_kmeans_seed(_desc_ref(desc), _ref(codes), u, _addr(centroids), _addr(picks), _addr(workspace),
+                                        int(workspace_bytes), stream if stream is not None else None))
+
+
+def _kmeans_workspace(desc, dev):
+    need = kmeans_workspace_bytes(desc)
+    if need == 0:
+        _check(kmeans_step_raw(desc, None, None, None, None, None, None, None, 0))          # raises with the descriptor's own code
+    return _empty_bytes(need, dev), need
+
+
+def kmeans_step(desc, codes, cin, cout=None, labels=None, counts=None, stats=None, workspace=None):
+    """One Lloyd iteration of include/stego_kmeans.h on torch's current stream, nothing synchronised.  cout: float32 [n, K] (may be
+    `cin`) or None for assignment only; labels: uint8 [B, h, w] or None; counts int64 [n] and stats float64 [4] are made when None;
+    workspace: what kmeans_workspace(desc, device) returned, for callers that step repeatedly.  -> (counts, stats)."""
+    _require_dev(codes, cin, cout, labels, counts, stats)
+    dev = codes.device
+    ws, need = workspace if workspace is not None else _kmeans_workspace(desc, dev)
+    if counts is None:
+        counts = torch.empty((desc.n,), dtype=torch.int64, device=dev)
+    if stats is None:
+        stats = torch.empty((4,), dtype=torch.float64, device=dev)
+    for name, t_, shape, dtype in (("centroids", cin, (desc.n, desc.K), torch.float32), ("out", cout, (desc.n, desc.K), torch.float32),
+                                   ("labels", labels, (desc.B, desc.h, desc.w), torch.uint8), ("counts", counts, (desc.n,), torch.int64),
+                                   ("stats", stats, (4,), torch.float64)):
+        if t_ is not None and (tuple(t_.shape) != shape or t_.dtype != dtype or not t_.is_contiguous()):
+            raise RuntimeError("kmeans_step: %s must be a contiguous %s tensor of shape %s, got %s %s"
+                               % (name, dtype, shape, t_.dtype, tuple(t_.shape)))
+    with _on_device(dev):
+        _check(kmeans_step_raw(desc, _map(codes), cin, cout, labels, counts, stats, ws, need, _stream()))
+    return counts, stats
+
+
+def kmeans_workspace(desc, dev):
+    """(workspace tensor, its bytes) for kmeans_step / kmeans_seed calls with this descriptor."""
+    return _kmeans_workspace(desc, dev)
+
+
+def kmeans_seed(desc, codes, u, workspace=None):
+    """k-means++ seeding of include/stego_kmeans.h: `u` is a sequence of n numbers in [0, 1) -> (centroids float32 [n, K], picks int64
+    [n]) on the codes' device, nothing synchronised."""
+    _require_dev(codes)
+    dev = codes.device
+    ws, need = workspace if workspace is not None else _kmeans_workspace(desc, dev)
+    draws = (ctypes.c_double * desc.n)(*[float(v) for v in u])
+    cent = torch.empty((desc.n, desc.K), dtype=torch.float32, device=dev)
+    picks = torch.empty((desc.n,), dtype=torch.int64, device=dev)
+    with _on_device(dev):
+        _check(kmeans_seed_raw(desc, _map(codes), draws, cent, picks, ws, need, _stream()))
+    return cent, picks
 
 
 # ---- device-side confusion matrices (include/stego_confusion.h; stego_amd.metrics wraps them for the trainer and evaluate())

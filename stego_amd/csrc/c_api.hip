@@ -23,6 +23,7 @@
 #include "../../include/stego_render.h"
 #include "../../include/stego_stats.h"
 #include "../../include/stego_pca.h"
+#include "../../include/stego_kmeans.h"
 #include "corr_wide.h"
 #include "launchers.h"
 
@@ -392,6 +393,9 @@ const char* stego_error_string(int code)
         case STEGO_ERR_PCA_SIZE: return "pca: B outside [1, 65535], h or w outside [1, 4096], more than 2^28 tokens, fewer than 4 tokens in a group, or H or W outside [1, 32768]";
         case STEGO_ERR_PCA_ITER: return "pca: n_iter outside [1, 256]";
         case STEGO_ERR_PCA_MODE: return "pca: group, resize or scale is none of its two values";
+        case STEGO_ERR_KMEANS_DIM: return "kmeans: K outside [1, 128] or n outside [1, 64] (include/stego_kmeans.h)";
+        case STEGO_ERR_KMEANS_SIZE: return "kmeans: B outside [1, 65535], h or w below 1, or more than 2^31 - 1 tokens";
+        case STEGO_ERR_KMEANS_DRAW: return "kmeans: a uniform number outside [0, 1)";
         case STEGO_ERR_CRF_RANGE: return "dense CRF: a lattice coordinate would leave the packed key (image too large for its standard deviations)";
         default: return code >= STEGO_ERR_HIP ? "HIP runtime error (code - 1000 = hipError_t)" : "unknown error";
     }

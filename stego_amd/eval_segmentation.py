@@ -79,6 +79,8 @@ def evaluate(model, loader, run_crf=True, device=None, fused_head=False, native_
     saved = {"index": [], "img": [], "label": [], "linear_preds": [], "cluster_preds": []}
     seen = 0
     device = device or next(model.parameters()).device
+    if hasattr(model, "check_cluster_scoring"):
+        model.check_cluster_scoring()
     model.eval()
     if native_metrics:
         from .metrics import DeviceUnsupervisedMetrics

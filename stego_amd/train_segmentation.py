@@ -80,14 +80,18 @@ class LitUnsupervisedSegmenter(nn.Module):
         else:
             raise ValueError("Unknown arch {}".format(cfg.arch))
         self.train_cluster_probe = ClusterLookup(dim, n_classes)
-        self.cluster_probe = ClusterLookup(dim, n_classes + cfg.extra_clusters)
+        # cfg.cluster_probe_n (a stego_amd extension, absent from shipped configs and old checkpoints): the cluster count of a probe that
+        # stego_amd.cluster_refit refitted; the metrics then treat what exceeds n_classes as extra clusters
+        probe_n = getattr(cfg, "cluster_probe_n", None)
+        cluster_extra = cfg.extra_clusters if probe_n is None else max(int(probe_n) - n_classes, 0)
+        self.cluster_probe = ClusterLookup(dim, n_classes + cfg.extra_clusters if probe_n is None else int(probe_n))
         self.linear_probe = nn.Conv2d(dim, n_classes, (1, 1))
         self.decoder = nn.Conv2d(dim, self.net.n_feats, (1, 1))
         # cfg.native_metrics: the confusion matrices stay on the device and validation_step scores with one fused call (stego_amd.metrics)
         Metrics = DeviceUnsupervisedMetrics if getattr(cfg, "native_metrics", False) else UnsupervisedMetrics
-        self.cluster_metrics = Metrics("test/cluster/", n_classes, cfg.extra_clusters, True)
+        self.cluster_metrics = Metrics("test/cluster/", n_classes, cluster_extra, True)
         self.linear_metrics = Metrics("test/linear/", n_classes, 0, False)
-        self.test_cluster_metrics = Metrics("final/cluster/", n_classes, cfg.extra_clusters, True)
+        self.test_cluster_metrics = Metrics("final/cluster/", n_classes, cluster_extra, True)
         self.test_linear_metrics = Metrics("final/linear/", n_classes, 0, False)
         self.linear_probe_loss_fn = nn.CrossEntropyLoss()
         self.crf_loss_fn = ContrastiveCRFLoss(cfg.crf_samples, cfg.alpha, cfg.beta, cfg.gamma, cfg.w1, cfg.w2, cfg.shift)
@@ -152,6 +156,15 @@ class LitUnsupervisedSegmenter(nn.Module):
         self._step_stats = None
         self._stats_tags = None
         self._stats_step0 = 0
+
+    def check_cluster_scoring(self):
+        """Scoring the cluster probe matches its clusters to the classes one to one: a refitted probe with fewer clusters than classes
+        cannot be scored (its pictures can be drawn: the clusters are then coloured by index)."""
+        probe_n = getattr(self.cfg, "cluster_probe_n", None)
+        if probe_n is not None and int(probe_n) < self.n_classes:
+            raise ValueError("cfg.cluster_probe_n = %d is below n_classes = %d: the cluster probe has fewer clusters than the dataset has "
+                             "classes and cannot be scored against them (refit it with at least %d clusters)"
+                             % (int(probe_n), self.n_classes, self.n_classes))
 
     @property
     def label_cmap(self):
@@ -451,6 +464,7 @@ class LitUnsupervisedSegmenter(nn.Module):
 
     def validation_step(self, batch, batch_idx):
         img, label = batch["img"], batch["label"]
+        self.check_cluster_scoring()
         self.net.eval()
         with torch.no_grad():
             _, code = self.net(img)
