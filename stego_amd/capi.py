@@ -272,6 +272,19 @@ KMEANS_ERR_DIM, KMEANS_ERR_SIZE, KMEANS_ERR_DRAW = 180, 181, 182
 KMEANS_MAX_K, KMEANS_MAX_N, KMEANS_MAX_B, KMEANS_MAX_TOKENS = 128, 64, 65535, (1 << 31) - 1
 KMEANS_FOLD, KMEANS_TILE, KMEANS_MAX_WORKGROUPS = 1024, 128, 512
 
+
+class StegoRegionsDesc(Structure):
+    """include/stego_regions.h"""
+    _fields_ = [(n, c_int32) for n in ("B", "H", "W", "connectivity", "label_dtype")]
+
+
+REGIONS_ERR_SIZE, REGIONS_ERR_CONN, REGIONS_ERR_DTYPE, REGIONS_ERR_LABELS, REGIONS_ERR_RANGE = 190, 191, 192, 193, 194
+REGIONS_I64, REGIONS_I32, REGIONS_U8 = 0, 1, 2
+REGIONS_DTYPES = {torch.int64: REGIONS_I64, torch.int32: REGIONS_I32, torch.uint8: REGIONS_U8}
+REGIONS_TILE, REGIONS_CHUNK, REGIONS_MAX_LABELS, REGIONS_LAUNCHES, REGIONS_MAX_B, REGIONS_MAX_PIXELS = 32, 2048, 256, 6, 65535, (1 << 31) - 1
+REGIONS_COLS32 = ("area", "y0", "x0", "y1", "x1", "first")
+REGIONS_COLS64 = ("label", "sum_y", "sum_x")
+
 # name -> (restype, argtypes); every symbol include/stego_corr.h declares
 _P = c_void_p
 _H = POINTER(StegoHeadDesc)
@@ -314,6 +327,12 @@ SIGNATURES = {
     "stego_kmeans_plan": (c_size_t, [POINTER(StegoKmeansDesc), POINTER(c_int32)]),
     "stego_kmeans_step": (c_int32, [POINTER(StegoKmeansDesc), _M, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "stego_kmeans_seed": (c_int32, [POINTER(StegoKmeansDesc), _M, _P, _P, _P, _P, c_size_t, _P]),
+    "stego_regions_workspace_bytes": (c_size_t, [POINTER(StegoRegionsDesc)]),
+    "stego_regions_plan": (c_int32, [POINTER(StegoRegionsDesc), POINTER(c_int32), POINTER(c_size_t), POINTER(c_int64)]),
+    "stego_regions_label": (c_int32, [POINTER(StegoRegionsDesc), _P, _P, _P, _P, _P, c_size_t, _P]),
+    "stego_regions_table": (c_int32, [POINTER(StegoRegionsDesc), _P, _P, _P, c_int64, _P, _P, _P]),
+    "stego_regions_votes": (c_int32, [POINTER(StegoRegionsDesc), _P, _P, _P, c_int64, _P, c_int64, c_int64, c_int32, _P, _P]),
+    "stego_regions_relabel": (c_int32, [POINTER(StegoRegionsDesc), _P, _P, _P, _P, c_int64, _P, _P, c_int64, c_int64, c_int32, _P, _P, _P]),
     "stego_probe_confusion": (c_int32, [POINTER(StegoProbeConfusionDesc), _M, _M] + [_P] * 6 + [_P]),
     "stego_probe_confusion_plan": (c_size_t, [POINTER(StegoProbeConfusionDesc), POINTER(c_int32), POINTER(c_int32)]),
     "stego_confusion": (c_int32, [POINTER(StegoConfusionDesc), _P, _P, _P, _P]),
@@ -1646,6 +1665,128 @@ def kmeans_seed(desc, codes, u, workspace=None):
     with _on_device(dev):
         _check(kmeans_seed_raw(desc, _map(codes), draws, cent, picks, ws, need, _stream()))
     return cent, picks
+
+
+# ---- segments as objects (include/stego_regions.h; stego_amd.regions wraps them)
+def regions_desc(B, H, W, connectivity=4, label_dtype=REGIONS_I64):
+    return StegoRegionsDesc(int(B), int(H), int(W), int(connectivity), int(label_dtype))
+
+
+def regions_workspace_bytes(desc):
+    """stego_regions_workspace_bytes (host only); 0 for an invalid descriptor."""
+    return int(load().stego_regions_workspace_bytes(byref(desc)))
+
+
+def regions_plan(desc):
+    """stego_regions_plan (host only) -> (return code, tile edge, [(LDS bytes, workgroups) of the six launches of regions_label])."""
+    tile = c_int32(-1)
+    lds, wgs = (c_size_t * REGIONS_LAUNCHES)(), (c_int64 * REGIONS_LAUNCHES)()
+    rc = load().stego_regions_plan(byref(desc), byref(tile), lds, wgs)
+    return int(rc), int(tile.value), [(int(a), int(b)) for a, b in zip(lds, wgs)]
+
+
+def regions_label_raw(desc, labels, ids, n_regions, root, workspace, workspace_bytes, stream=None):
+    """stego_regions_label with every argument given (tensors, raw addresses or None) -> the return code, unchecked."""
+    return int(load().stego_regions_label(_desc_ref(desc), _addr(labels), _addr(ids), _addr(n_regions), _addr(root), _addr(workspace),
+                                          int(workspace_bytes), stream if stream is not None else None))
+
+
+def regions_table_raw(desc, labels, ids, row_offset, capacity, cols32, cols64, stream=None):
+    return int(load().stego_regions_table(_desc_ref(desc), _addr(labels), _addr(ids), _addr(row_offset), int(capacity), _addr(cols32),
+                                          _addr(cols64), stream if stream is not None else None))
+
+
+def regions_votes_raw(desc, labels, ids, row_offset, capacity, small_rank, lo, hi, n_labels, votes, stream=None):
+    return int(load().stego_regions_votes(_desc_ref(desc), _addr(labels), _addr(ids), _addr(row_offset), int(capacity), _addr(small_rank),
+                                          int(lo), int(hi), int(n_labels), _addr(votes), stream if stream is not None else None))
+
+
+def regions_relabel_raw(desc, labels_in, labels_out, ids, row_offset, capacity, small_rank, first, lo, hi, n_labels, votes, changed,
+                        stream=None):
+    return int(load().stego_regions_relabel(_desc_ref(desc), _addr(labels_in), _addr(labels_out), _addr(ids), _addr(row_offset),
+                                            int(capacity), _addr(small_rank), _addr(first), int(lo), int(hi), int(n_labels), _addr(votes),
+                                            _addr(changed), stream if stream is not None else None))
+
+
+def _regions_desc_of(labels, connectivity):
+    if labels.dim() != 3 or labels.dtype not in REGIONS_DTYPES or not labels.is_contiguous():
+        raise RuntimeError("regions: labels must be a contiguous int64, int32 or uint8 [B, H, W] tensor, got %s %s"
+                           % (labels.dtype, tuple(labels.shape)))
+    B, H, W = labels.shape
+    return regions_desc(B, H, W, connectivity, REGIONS_DTYPES[labels.dtype])
+
+
+def _regions_int32(name, t_, shape):
+    if t_.dtype != torch.int32 or tuple(t_.shape) != tuple(shape) or not t_.is_contiguous():
+        raise RuntimeError("regions: %s must be a contiguous int32 tensor of shape %s, got %s %s" % (name, tuple(shape), t_.dtype, tuple(t_.shape)))
+
+
+def regions_label(labels, connectivity=4):
+    """stego_regions_label on torch's current stream, nothing synchronised -> (ids int32 [B, H, W], n_regions int32 [B], root int32
+    [B, H, W])."""
+    _require_dev(labels)
+    desc = _regions_desc_of(labels, connectivity)
+    need = regions_workspace_bytes(desc)
+    if need == 0:
+        _check(regions_label_raw(desc, None, None, None, None, None, 0))             # raises with the descriptor's own code
+    dev = labels.device
+    ids = torch.empty(labels.shape, dtype=torch.int32, device=dev)
+    root = torch.empty(labels.shape, dtype=torch.int32, device=dev)
+    n_regions = torch.empty((labels.shape[0],), dtype=torch.int32, device=dev)
+    ws = _empty_bytes(need, dev)
+    with _on_device(dev):
+        _check(regions_label_raw(desc, labels, ids, n_regions, root, ws, need, _stream()))
+    return ids, n_regions, root
+
+
+def regions_table(labels, ids, row_offset, capacity):
+    """stego_regions_table -> (cols32 int32 [6, capacity]: area, y0, x0, y1, x1, first; cols64 int64 [3, capacity]: label, sum_y, sum_x).
+    row_offset: int64 [B], the first row of every image."""
+    _require_dev(labels, ids, row_offset)
+    desc = _regions_desc_of(labels, 4)
+    _regions_int32("ids", ids, labels.shape)
+    if row_offset.dtype != torch.int64 or tuple(row_offset.shape) != (labels.shape[0],) or not row_offset.is_contiguous():
+        raise RuntimeError("regions: row_offset must be a contiguous int64 [B] tensor")
+    dev = labels.device
+    cols32 = torch.empty((len(REGIONS_COLS32), int(capacity)), dtype=torch.int32, device=dev)
+    cols64 = torch.empty((len(REGIONS_COLS64), int(capacity)), dtype=torch.int64, device=dev)
+    with _on_device(dev):
+        _check(regions_table_raw(desc, labels, ids, row_offset, capacity, cols32, cols64, _stream()))
+    return cols32, cols64
+
+
+def regions_votes(labels, ids, row_offset, small_rank, lo, hi, n_labels, votes=None):
+    """stego_regions_votes -> votes int32 [hi - lo, n_labels] (reset by the call)."""
+    _require_dev(labels, ids, row_offset, small_rank, votes)
+    desc = _regions_desc_of(labels, 4)
+    _regions_int32("ids", ids, labels.shape)
+    _regions_int32("small_rank", small_rank, (small_rank.numel(),))
+    rows = max(int(hi) - int(lo), 0)
+    if votes is None:
+        votes = torch.empty((rows, max(int(n_labels), 0)), dtype=torch.int32, device=labels.device)
+    elif votes.dtype != torch.int32 or votes.numel() < rows * int(n_labels) or not votes.is_contiguous():
+        raise RuntimeError("regions: votes must be a contiguous int32 tensor of at least (hi - lo) * n_labels elements")
+    with _on_device(labels.device):
+        _check(regions_votes_raw(desc, labels, ids, row_offset, small_rank.numel(), small_rank, lo, hi, n_labels, votes, _stream()))
+    return votes
+
+
+def regions_relabel(labels_in, labels_out, ids, row_offset, small_rank, first, lo, hi, n_labels, votes, changed):
+    """stego_regions_relabel: the small regions of ranks [lo, hi) rewritten in labels_out, changed int32 [1] += the regions that changed."""
+    _require_dev(labels_in, labels_out, ids, row_offset, small_rank, first, votes, changed)
+    desc = _regions_desc_of(labels_in, 4)
+    if labels_out.dtype != labels_in.dtype or labels_out.shape != labels_in.shape or not labels_out.is_contiguous() or \
+            labels_out.data_ptr() == labels_in.data_ptr():
+        raise RuntimeError("regions: labels_out must be another contiguous tensor of labels_in's dtype and shape")
+    _regions_int32("ids", ids, labels_in.shape)
+    _regions_int32("small_rank", small_rank, (small_rank.numel(),))
+    _regions_int32("first", first, (small_rank.numel(),))
+    _regions_int32("changed", changed, (1,))
+    if votes.dtype != torch.int32 or votes.numel() < max(int(hi) - int(lo), 0) * int(n_labels) or not votes.is_contiguous():
+        raise RuntimeError("regions: votes must be a contiguous int32 tensor of at least (hi - lo) * n_labels elements")
+    with _on_device(labels_in.device):
+        _check(regions_relabel_raw(desc, labels_in, labels_out, ids, row_offset, small_rank.numel(), small_rank, first, lo, hi, n_labels,
+                                   votes, changed, _stream()))
 
 
 # ---- device-side confusion matrices (include/stego_confusion.h; stego_amd.metrics wraps them for the trainer and evaluate())

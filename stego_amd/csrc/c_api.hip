@@ -24,6 +24,7 @@
 #include "../../include/stego_stats.h"
 #include "../../include/stego_pca.h"
 #include "../../include/stego_kmeans.h"
+#include "../../include/stego_regions.h"
 #include "corr_wide.h"
 #include "launchers.h"
 
@@ -396,6 +397,11 @@ const char* stego_error_string(int code)
         case STEGO_ERR_KMEANS_DIM: return "kmeans: K outside [1, 128] or n outside [1, 64] (include/stego_kmeans.h)";
         case STEGO_ERR_KMEANS_SIZE: return "kmeans: B outside [1, 65535], h or w below 1, or more than 2^31 - 1 tokens";
         case STEGO_ERR_KMEANS_DRAW: return "kmeans: a uniform number outside [0, 1)";
+        case STEGO_ERR_REGIONS_SIZE: return "regions: B outside [1, 65535], H or W below 1, or H * W not below 2^31 (include/stego_regions.h)";
+        case STEGO_ERR_REGIONS_CONN: return "regions: connectivity is neither 4 nor 8";
+        case STEGO_ERR_REGIONS_DTYPE: return "regions: label_dtype is none of STEGO_REGIONS_I64, STEGO_REGIONS_I32, STEGO_REGIONS_U8";
+        case STEGO_ERR_REGIONS_LABELS: return "regions: n_labels outside [1, 256]";
+        case STEGO_ERR_REGIONS_RANGE: return "regions: a negative capacity, lo < 0, hi < lo, or a vote table beyond 2^31 - 1 words";
         case STEGO_ERR_CRF_RANGE: return "dense CRF: a lattice coordinate would leave the packed key (image too large for its standard deviations)";
         default: return code >= STEGO_ERR_HIP ? "HIP runtime error (code - 1000 = hipError_t)" : "unknown error";
     }

@@ -28,6 +28,14 @@ nothing there.
 With `save_salience=True` every image also gets its attention salience mask (stego_amd.salience: the strongest patches holding
 `salience_keep` of the class token's attention in the backbone's last block) as `salience/NAME.png` (0 / 255) and, beside the image,
 as `salience_sheet/NAME.png`.  It costs one more backbone pass per batch and, like `save_pca`, writes nothing under `full_res`.
+
+With `min_region_area` > 0 both probes' label maps are cleaned on the device before anything is written (stego_amd.regions,
+csrc/regions.hip): a connected region - `region_connectivity` 4 or 8 - with fewer pixels takes the label most of its neighbours
+have.  `linear/`, `cluster/`, the colour pictures and the regions then all show the cleaned maps.  With `save_regions=True` every
+image also gets `regions/NAME.json`, the table of the connected regions of its cluster map (id, label, class - through
+`model.cluster_to_class` when the checkpoint stores one -, area, box, centroid, first pixel), and the id map itself as
+`region_ids/NAME.png`, a 16-bit PNG (mode "I;16"), or as `region_ids/NAME.npy` (int32) from 65536 regions on; the JSON names the
+file ("id_map").  Both work under `full_res`: the canvas is a larger label map.  The returned list is the same with and without them.
 """
 import os
 import sys
@@ -169,6 +177,26 @@ def my_app(cfg):
             Image.fromarray(mask[j]).save(join(out, "salience", prediction_name(name)))
             Image.fromarray(sheet[j]).save(join(out, "salience_sheet", prediction_name(name)))
 
+    min_area = int(getattr(cfg, "min_region_area", 0))
+    connectivity = int(getattr(cfg, "region_connectivity", 4))
+    save_regions = getattr(cfg, "save_regions", False)
+    if save_regions:
+        from .regions import label_regions, region_table, write_id_map, write_regions
+        for sub in ("regions", "region_ids"):
+            os.makedirs(join(out, sub), exist_ok=True)
+
+    def save_region_files(names, cluster):
+        """The region table and the id map of every image of a batch: cluster [N, H, W] on the device."""
+        cluster = cluster.contiguous()
+        ids, counts = label_regions(cluster, connectivity)
+        table = region_table(cluster, ids, counts)
+        ids = ids.cpu().numpy()
+        for j, name in enumerate(names):
+            stem = os.path.splitext(name)[0]
+            id_map = write_id_map(join(out, "region_ids", stem), ids[j], table.n_regions[j])
+            write_regions(join(out, "regions", stem + ".json"), table, j, cluster.shape[1], cluster.shape[2], connectivity,
+                          class_of=model.cluster_to_class, id_map=os.path.basename(id_map))
+
     if getattr(cfg, "full_res", False):
         dataset = UnlabeledImageFolder(cfg.image_dir, full_image_transform(cfg.res))
         loader = torch.utils.data.DataLoader(dataset, 1, shuffle=False, num_workers=cfg.num_workers, collate_fn=first)
@@ -178,7 +206,10 @@ def my_app(cfg):
                 continue
             img = img.to(dev)
             linear, cluster = segment_large(model, img, window=cfg.res, stride=getattr(cfg, "window_stride", None),
-                                            batch=cfg.batch_size * 2, run_crf=run_crf)
+                                            batch=cfg.batch_size * 2, run_crf=run_crf, min_region_area=min_area,
+                                            connectivity=connectivity)
+            if save_regions:
+                save_region_files([name], cluster.unsqueeze(0))
             if save_color:
                 save_colors([name], img.unsqueeze(0), linear.unsqueeze(0), cluster.unsqueeze(0))
             save(name, linear.cpu().numpy(), cluster.cpu().numpy())
@@ -194,7 +225,9 @@ def my_app(cfg):
             continue
         imgs = imgs.to(dev)
         maps = {} if save_pca else None
-        linear, cluster = segment(model, imgs, run_crf=run_crf, maps=maps)
+        linear, cluster = segment(model, imgs, run_crf=run_crf, maps=maps, min_region_area=min_area, connectivity=connectivity)
+        if save_regions:
+            save_region_files(names, cluster)
         if save_color:
             save_colors(names, imgs, linear, cluster)
         if save_pca:

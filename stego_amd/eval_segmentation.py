@@ -63,7 +63,8 @@ def _kept_preds(model, img, code1, code2, size, run_crf):
     return probe_head(model, code1, code2, size, linear="argmax", cluster="argmax")
 
 
-def evaluate(model, loader, run_crf=True, device=None, fused_head=False, native_metrics=False, keep=None):
+def evaluate(model, loader, run_crf=True, device=None, fused_head=False, native_metrics=False, keep=None, min_region_area=0,
+             region_connectivity=4):
     """eval_segmentation.py:118-161 over `loader` (batches with "img" / "label", or (img, label, ...) tuples) -> the metrics dict of
     model.test_linear_metrics and model.test_cluster_metrics (reset first, then updated batch by batch, then computed).
     fused_head: the flip average, resize and both probes in one launch (stego_amd.segment.probe_head), which writes the CRF's
@@ -73,7 +74,11 @@ def evaluate(model, loader, run_crf=True, device=None, fused_head=False, native_
     keep: indices of images, counted through the loader, whose image, label and both predictions stay on the device: afterwards
     model.saved_data = {"index": [...], "img": [n, 3, H, W], "label", "linear_preds", "cluster_preds": [n, h, w]} in the order the
     loader met them (the reference's saved_data).  With native_metrics the batches that hold one additionally run the fused head with
-    the argmax output, since the metrics path has no label map; the metrics do not change."""
+    the argmax output, since the metrics path has no label map; the metrics do not change.
+    min_region_area > 0: the small-region cleanup of stego_amd.regions (regions under `region_connectivity`) on both predictions, after
+    the CRF or the argmax and before they are scored.  With native_metrics the label maps are then made (the fused head's argmax, after
+    the CRF with run_crf), cleaned and counted by the label-map confusion launch: the fused code-to-matrix launch never makes a map."""
+    min_region_area = int(min_region_area)
     keeping = keep is not None
     keep = set(int(k) for k in keep) if keeping else set()
     saved = {"index": [], "img": [], "label": [], "linear_preds": [], "cluster_preds": []}
@@ -98,6 +103,15 @@ def evaluate(model, loader, run_crf=True, device=None, fused_head=False, native_
             _, code2 = model.net(img.flip(dims=[3]))
             wanted = [j for j in range(img.shape[0]) if seen + j in keep]
             first, seen = seen, seen + img.shape[0]
+            if native_metrics and min_region_area > 0:
+                from .segment import _clean
+                linear_preds, cluster_preds = _clean(model, *_kept_preds(model, img, code1, code2, label.shape[-2:], run_crf),
+                                                     min_region_area, region_connectivity)
+                model.test_linear_metrics.update(linear_preds, label)
+                model.test_cluster_metrics.update(cluster_preds, label)
+                if wanted:
+                    _keep(saved, wanted, first, img, label, linear_preds, cluster_preds)
+                continue
             if native_metrics:
                 _native_update(model, img, code1, code2, label, run_crf)
                 if wanted:
@@ -116,6 +130,9 @@ def evaluate(model, loader, run_crf=True, device=None, fused_head=False, native_
                 else:
                     linear_preds = linear_probs.argmax(1)
                     cluster_preds = cluster_probs.argmax(1)
+            if min_region_area > 0:
+                from .segment import _clean
+                linear_preds, cluster_preds = _clean(model, linear_preds, cluster_preds, min_region_area, region_connectivity)
             model.test_linear_metrics.update(linear_preds, label)
             model.test_cluster_metrics.update(cluster_preds, label)
             if wanted:
@@ -205,7 +222,8 @@ def my_app(cfg):
         model = LitUnsupervisedSegmenter.load_from_checkpoint(model_path)
         model.eval().to(dev)
         metrics = evaluate(model, make_loader(cfg, model), run_crf=cfg.run_crf, device=dev, fused_head=getattr(cfg, "fused_head", False),
-                           native_metrics=getattr(cfg, "native_metrics", False), keep=keep)
+                           native_metrics=getattr(cfg, "native_metrics", False), keep=keep,
+                           min_region_area=getattr(cfg, "min_region_area", 0), region_connectivity=getattr(cfg, "region_connectivity", 4))
         if figures:
             save_figures(model, result_dir(cfg, i))
         print("")

@@ -40,12 +40,24 @@ def probe_head(model, code, code_flip, size, linear="log_probs", cluster="log_pr
                                linear, cluster, alpha)
 
 
-def segment(model, img, run_crf=True, flip=True, res=None, maps=None):
+def _clean(model, lin, clu, min_region_area, connectivity):
+    """The small-region cleanup of stego_amd.regions on both probes' label maps (a probe's label count is its n_labels)."""
+    from .regions import clean_label_maps
+    return (clean_label_maps(lin, min_region_area, int(model.linear_probe.weight.shape[0]), connectivity),
+            clean_label_maps(clu, min_region_area, int(model.cluster_probe.clusters.shape[0]), connectivity))
+
+
+def segment(model, img, run_crf=True, flip=True, res=None, maps=None, min_region_area=0, connectivity=4):
     """Normalised images [B, 3, H, W] -> (linear_preds, cluster_preds), int64 [B, res, res] (default: the images' H, W): the backbone
     on the images and on their mirror images, the fused probe head, then the dense CRF on both probes' probabilities (run_crf) and
     the argmax.  The CRF runs at the image's resolution, so `res` must equal it when run_crf is set.
     maps: a dict that receives what the backbone returned for the unflipped images, "feats" [B, C, h, w] and "code" [B, K, h, w]
-    (stego_amd.feature_pca draws them); nothing else changes."""
+    (stego_amd.feature_pca draws them); nothing else changes.
+    min_region_area > 0: regions of either map (connected under `connectivity`, 4 or 8) with fewer pixels take the label most of their
+    neighbours have (stego_amd.regions.merge_small_regions, on the device); 0 is the path without it."""
+    if int(min_region_area) > 0:
+        lin, clu = segment(model, img, run_crf=run_crf, flip=flip, res=res, maps=maps)
+        return _clean(model, lin, clu, int(min_region_area), connectivity)
     _device_tensor(img, "img")
     if img.dim() != 4 or img.shape[1] != 3:
         raise ValueError("img: expected [B, 3, H, W], got %s" % (tuple(img.shape),))
@@ -121,13 +133,16 @@ def _segment_large_one(model, img, window, stride, batch, run_crf, flip):
     return lin, dense_crf_batch(bgr, clu.unsqueeze(0)).argmax(1)[0]
 
 
-def segment_large(model, img, window, stride=None, batch=16, run_crf=True, flip=True):
+def segment_large(model, img, window, stride=None, batch=16, run_crf=True, flip=True, min_region_area=0, connectivity=4):
     """A normalised image [3, H, W] of any size with H, W >= window (or [B, 3, H, W], image by image) -> (linear_preds,
     cluster_preds), int64 [H, W] (or [B, H, W]).  The image is cut into overlapping window x window pieces `stride` apart (default
     ceil(window / 2); window <= 2 * stride <= 2 * window; the last window of a row or column is shifted back to end at the edge), the
     windows - and their mirror images when `flip` - go through the backbone `batch` at a time, and one stitch_probe launch blends the
     windows' logits per pixel with tent weights and writes the canvas: the label maps directly, or the probabilities for the dense
-    CRF (run_crf), which then runs on the whole canvas."""
+    CRF (run_crf), which then runs on the whole canvas.  min_region_area, connectivity: as in segment(), on the canvas."""
+    if int(min_region_area) > 0:
+        lin, clu = segment_large(model, img, window, stride=stride, batch=batch, run_crf=run_crf, flip=flip)
+        return _clean(model, lin, clu, int(min_region_area), connectivity)
     if not torch.is_tensor(img):
         raise TypeError("img: expected a torch tensor, got %s" % type(img).__name__)
     if img.dim() not in (3, 4) or img.shape[-3] != 3:
