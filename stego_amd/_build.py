@@ -23,7 +23,7 @@ INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB_DIR = os.path.join(HERE, "lib")
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 LIB_PATH = os.path.join(LIB_DIR, "libstego_corr.so")
-SOURCES = ["corr_sample.hip", "corr_fwd.hip", "corr_fused.hip", "corr_fused_odd.hip", "corr_fused_c192.hip", "corr_fused_half.hip", "corr_bwd.hip", "corr_bwd_lists.hip", "knn_topk.hip", "dense_corr.hip", "dense_stream.hip", "sample_sets.hip", "loss_pointwise.hip", "corr_wide.hip", "vit_forward.hip", "vit_cls_attn.hip", "host_util.hip", "draws.hip", "head_fused.hip", "dense_crf.hip", "batch_prep.hip", "batch_prep_dir.hip", "salience_draw.hip", "probe_head.hip", "probe_train.hip", "corr_pr.hip", "corr_heat.hip", "crf_loss.hip", "augment.hip", "confusion.hip", "optim_step.hip", "stitch_probe.hip", "rec_loss.hip", "render.hip", "step_stats.hip", "feature_pca.hip", "code_kmeans.hip", "regions.hip", "c_api.hip"]
+SOURCES = ["corr_sample.hip", "corr_fwd.hip", "corr_fused.hip", "corr_fused_odd.hip", "corr_fused_c192.hip", "corr_fused_half.hip", "corr_bwd.hip", "corr_bwd_lists.hip", "knn_topk.hip", "dense_corr.hip", "dense_stream.hip", "sample_sets.hip", "loss_pointwise.hip", "corr_wide.hip", "vit_forward.hip", "vit_cls_attn.hip", "host_util.hip", "draws.hip", "head_fused.hip", "dense_crf.hip", "batch_prep.hip", "batch_prep_dir.hip", "salience_draw.hip", "probe_head.hip", "probe_train.hip", "corr_pr.hip", "corr_heat.hip", "crf_loss.hip", "augment.hip", "confusion.hip", "optim_step.hip", "stitch_probe.hip", "rec_loss.hip", "render.hip", "step_stats.hip", "feature_pca.hip", "code_kmeans.hip", "regions.hip", "region_pool.hip", "c_api.hip"]
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 LDFLAGS = ["--offload-arch=gfx950", "-fPIC", "-shared"]
 # the one torch C++ extension (host only, g++): the autograd function of the loss and the generator's graph-safe Philox state, over the C ABI

@@ -285,6 +285,14 @@ REGIONS_TILE, REGIONS_CHUNK, REGIONS_MAX_LABELS, REGIONS_LAUNCHES, REGIONS_MAX_B
 REGIONS_COLS32 = ("area", "y0", "x0", "y1", "x1", "first")
 REGIONS_COLS64 = ("label", "sum_y", "sum_x")
 
+class StegoRegionPoolDesc(Structure):
+    """include/stego_region_pool.h"""
+    _fields_ = [(n, c_int32) for n in ("B", "C", "h", "w", "H", "W")] + [("rows", c_int64)]
+
+
+REGION_POOL_ERR_SIZE, REGION_POOL_ERR_DIM, REGION_POOL_ERR_RANGE = 200, 201, 202
+REGION_POOL_MAX_C, REGION_POOL_CB, REGION_POOL_PARTIALS, REGION_POOL_LAUNCHES = 2048, 128, 1024, 3
+
 # name -> (restype, argtypes); every symbol include/stego_corr.h declares
 _P = c_void_p
 _H = POINTER(StegoHeadDesc)
@@ -333,6 +341,9 @@ SIGNATURES = {
     "stego_regions_table": (c_int32, [POINTER(StegoRegionsDesc), _P, _P, _P, c_int64, _P, _P, _P]),
     "stego_regions_votes": (c_int32, [POINTER(StegoRegionsDesc), _P, _P, _P, c_int64, _P, c_int64, c_int64, c_int32, _P, _P]),
     "stego_regions_relabel": (c_int32, [POINTER(StegoRegionsDesc), _P, _P, _P, _P, c_int64, _P, _P, c_int64, c_int64, c_int32, _P, _P, _P]),
+    "stego_region_pool_workspace_bytes": (c_size_t, [POINTER(StegoRegionPoolDesc)]),
+    "stego_region_pool_plan": (c_int32, [POINTER(StegoRegionPoolDesc), POINTER(c_int32), POINTER(c_int32), POINTER(c_size_t), POINTER(c_int64)]),
+    "stego_region_pool": (c_int32, [POINTER(StegoRegionPoolDesc), _M, _P, _P, _P, c_int64, c_int64, c_int64, _P, _P, c_size_t, _P]),
     "stego_probe_confusion": (c_int32, [POINTER(StegoProbeConfusionDesc), _M, _M] + [_P] * 6 + [_P]),
     "stego_probe_confusion_plan": (c_size_t, [POINTER(StegoProbeConfusionDesc), POINTER(c_int32), POINTER(c_int32)]),
     "stego_confusion": (c_int32, [POINTER(StegoConfusionDesc), _P, _P, _P, _P]),
@@ -1787,6 +1798,62 @@ def regions_relabel(labels_in, labels_out, ids, row_offset, small_rank, first, l
     with _on_device(labels_in.device):
         _check(regions_relabel_raw(desc, labels_in, labels_out, ids, row_offset, small_rank.numel(), small_rank, first, lo, hi, n_labels,
                                    votes, changed, _stream()))
+
+
+# ---- region descriptors (include/stego_region_pool.h; stego_amd.region_descriptors wraps them)
+def region_pool_desc(B, C, h, w, H, W, rows):
+    return StegoRegionPoolDesc(int(B), int(C), int(h), int(w), int(H), int(W), int(rows))
+
+
+def region_pool_workspace_bytes(desc):
+    """stego_region_pool_workspace_bytes (host only); 0 for an invalid descriptor."""
+    return int(load().stego_region_pool_workspace_bytes(byref(desc)))
+
+
+def region_pool_plan(desc):
+    """stego_region_pool_plan (host only) -> (return code, segment length in pixels, channel block, [(LDS bytes, workgroups) of the
+    range, pool and finish launches])."""
+    seg, cb = c_int32(-1), c_int32(-1)
+    lds, wgs = (c_size_t * REGION_POOL_LAUNCHES)(), (c_int64 * REGION_POOL_LAUNCHES)()
+    rc = load().stego_region_pool_plan(byref(desc), byref(seg), byref(cb), lds, wgs)
+    return int(rc), int(seg.value), int(cb.value), [(int(a), int(b)) for a, b in zip(lds, wgs)]
+
+
+def region_pool_raw(desc, map_, ids, row_offset, area, capacity, lo, hi, out, workspace, workspace_bytes, stream=None):
+    """stego_region_pool with every argument given (a StegoMap or None; tensors, raw addresses or None) -> the return code, unchecked."""
+    return int(load().stego_region_pool(_desc_ref(desc), _ref(map_), _addr(ids), _addr(row_offset), _addr(area), int(capacity), int(lo),
+                                        int(hi), _addr(out), _addr(workspace), int(workspace_bytes),
+                                        stream if stream is not None else None))
+
+
+def region_pool(maps, ids, row_offset, area, lo, hi, out=None, workspace=None):
+    """stego_region_pool on torch's current stream, nothing synchronised: maps float32 [B, C, h, w] (any strides), ids int32 [B, H, W],
+    row_offset int64 [B], area int32 [capacity] -> float32 [hi - lo, C], the descriptors of the table rows [lo, hi).  `out` and
+    `workspace` (uint8, from an earlier call of at least as many rows) are reused when given."""
+    _require_dev(maps, ids, row_offset, area, out, workspace)
+    m = _map(maps)
+    if ids.dim() != 3 or ids.dtype != torch.int32 or not ids.is_contiguous() or ids.shape[0] != maps.shape[0]:
+        raise RuntimeError("region_pool: ids must be a contiguous int32 [%d, H, W] tensor, got %s %s" % (maps.shape[0], ids.dtype, tuple(ids.shape)))
+    if row_offset.dtype != torch.int64 or tuple(row_offset.shape) != (maps.shape[0],) or not row_offset.is_contiguous():
+        raise RuntimeError("region_pool: row_offset must be a contiguous int64 [B] tensor")
+    if area.dtype != torch.int32 or area.dim() != 1 or not area.is_contiguous():
+        raise RuntimeError("region_pool: area must be a contiguous int32 [capacity] tensor")
+    B, C, h, w = maps.shape
+    rows = max(int(hi) - int(lo), 0)
+    desc = region_pool_desc(B, C, h, w, ids.shape[1], ids.shape[2], rows)
+    need = region_pool_workspace_bytes(desc)
+    if need == 0:
+        _check(region_pool_raw(desc, None, None, None, None, 0, 0, 0, None, None, 0))      # raises with the descriptor's own code
+    dev = maps.device
+    if out is None:
+        out = torch.empty((rows, C), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.numel() < rows * C or not out.is_contiguous():
+        raise RuntimeError("region_pool: out must be a contiguous float32 tensor of at least (hi - lo) * C elements")
+    if workspace is None or workspace.numel() < need:
+        workspace = _empty_bytes(need, dev)
+    with _on_device(dev):
+        _check(region_pool_raw(desc, m, ids, row_offset, area, area.numel(), lo, hi, out, workspace, workspace.numel(), _stream()))
+    return out
 
 
 # ---- device-side confusion matrices (include/stego_confusion.h; stego_amd.metrics wraps them for the trainer and evaluate())

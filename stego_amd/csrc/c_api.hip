@@ -25,6 +25,7 @@
 #include "../../include/stego_pca.h"
 #include "../../include/stego_kmeans.h"
 #include "../../include/stego_regions.h"
+#include "../../include/stego_region_pool.h"
 #include "corr_wide.h"
 #include "launchers.h"
 
@@ -402,6 +403,9 @@ const char* stego_error_string(int code)
         case STEGO_ERR_REGIONS_DTYPE: return "regions: label_dtype is none of STEGO_REGIONS_I64, STEGO_REGIONS_I32, STEGO_REGIONS_U8";
         case STEGO_ERR_REGIONS_LABELS: return "regions: n_labels outside [1, 256]";
         case STEGO_ERR_REGIONS_RANGE: return "regions: a negative capacity, lo < 0, hi < lo, or a vote table beyond 2^31 - 1 words";
+        case STEGO_ERR_REGION_POOL_SIZE: return "region pool: B outside [1, 65535], a side of the map or of the id map below 1, or H * W or h * w not below 2^31 (include/stego_region_pool.h)";
+        case STEGO_ERR_REGION_POOL_DIM: return "region pool: C outside [1, 2048]";
+        case STEGO_ERR_REGION_POOL_RANGE: return "region pool: rows < 0, lo < 0, hi < lo, hi > capacity, or (hi - lo) * C not below 2^31";
         case STEGO_ERR_CRF_RANGE: return "dense CRF: a lattice coordinate would leave the packed key (image too large for its standard deviations)";
         default: return code >= STEGO_ERR_HIP ? "HIP runtime error (code - 1000 = hipError_t)" : "unknown error";
     }

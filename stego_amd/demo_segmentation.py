@@ -36,6 +36,9 @@ image also gets `regions/NAME.json`, the table of the connected regions of its c
 `model.cluster_to_class` when the checkpoint stores one -, area, box, centroid, first pixel), and the id map itself as
 `region_ids/NAME.png`, a 16-bit PNG (mode "I;16"), or as `region_ids/NAME.npy` (int32) from 65536 regions on; the JSON names the
 file ("id_map").  Both work under `full_res`: the canvas is a larger label map.  The returned list is the same with and without them.
+With `save_region_index=True` as well, the `code` the backbone returned (`region_descriptor: "feats"` for its features), its tokens
+L2-normalised, is pooled over every region on the device (stego_amd.region_descriptors, csrc/region_pool.hip) and the folder's
+`regions/index.npz` is written for `python -m stego_amd.find_objects`.  Under `full_res` no index is written, and the run says so.
 """
 import os
 import sys
@@ -185,11 +188,24 @@ def my_app(cfg):
         for sub in ("regions", "region_ids"):
             os.makedirs(join(out, sub), exist_ok=True)
 
-    def save_region_files(names, cluster):
-        """The region table and the id map of every image of a batch: cluster [N, H, W] on the device."""
+    region_index = None
+    if save_regions and getattr(cfg, "save_region_index", False):
+        if getattr(cfg, "full_res", False):
+            print("save_region_index: no index under full_res (an image is a set of windows there, each with a map of its own)")
+        else:
+            from .region_descriptors import RegionIndex, region_descriptors
+            region_index = RegionIndex(getattr(cfg, "region_descriptor", "code"))
+
+    def save_region_files(names, cluster, maps=None):
+        """The region table and the id map of every image of a batch: cluster [N, H, W] on the device.  With the backbone's `maps`
+        the regions' descriptors go into the folder's index."""
         cluster = cluster.contiguous()
         ids, counts = label_regions(cluster, connectivity)
         table = region_table(cluster, ids, counts)
+        if region_index is not None:
+            pooled = region_descriptors(ids, table, maps[region_index.pooled].detach().float(), normalize=True)
+            for j, name in enumerate(names):
+                region_index.add(name, table, j, pooled[table.rows(j)])
         ids = ids.cpu().numpy()
         for j, name in enumerate(names):
             stem = os.path.splitext(name)[0]
@@ -224,10 +240,10 @@ def my_app(cfg):
         if imgs is None:
             continue
         imgs = imgs.to(dev)
-        maps = {} if save_pca else None
+        maps = {} if save_pca or region_index is not None else None
         linear, cluster = segment(model, imgs, run_crf=run_crf, maps=maps, min_region_area=min_area, connectivity=connectivity)
         if save_regions:
-            save_region_files(names, cluster)
+            save_region_files(names, cluster, maps)
         if save_color:
             save_colors(names, imgs, linear, cluster)
         if save_pca:
@@ -237,6 +253,8 @@ def my_app(cfg):
         linear, cluster = linear.cpu().numpy(), cluster.cpu().numpy()
         for j, name in enumerate(names):
             save(name, linear[j], cluster[j])
+    if region_index is not None:
+        region_index.save(join(out, "regions", "index.npz"))
     if skipped:
         print("skipped %d file(s) PIL cannot read: %s" % (len(skipped), ", ".join(skipped)))
     return written
