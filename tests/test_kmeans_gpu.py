@@ -26,7 +26,13 @@ STEP_SHAPES = [(3, 7, 5, 70, 27),          # ragged tile, the shipped K and n
                (2, 40, 40, 128, 64),       # the limits
                (3, 7, 5, 3, 5),            # small K
                (1, 1, 1, 70, 1),           # one token, one cluster
-               (2, 9, 9, 33, 2)]           # odd K
+               (2, 9, 9, 33, 2),           # odd K
+               # kmeans_assign_kernel<NT, CT, DENSE>, NT = ceil(n / 32), CT = ceil(K / 32): the rows above reach <1,1> <1,2> <1,3> <2,3>
+               # <2,4>; these the rest of dispatch_assign's table, each under the three layouts (DENSE and not)
+               (2, 6, 5, 40, 5),           # <1,2> once more, K between the tiles
+               (1, 9, 17, 128, 27),        # <1,4>: 153 tokens, a second 128-token tile of 25
+               (2, 8, 9, 20, 40),          # <2,1>
+               (3, 11, 13, 64, 64)]        # <2,2>: both counts at a tile's edge, 429 tokens in four tiles
 SEED_SHAPES = [(3, 7, 5, 70, 5), (2, 40, 40, 70, 33)]
 LAYOUTS = ["nchw", "cl", "cl_view"]
 MARGIN = 1e-5

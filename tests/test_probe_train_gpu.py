@@ -109,6 +109,7 @@ CASES = [  # (B, K, h, w, H, W, n_lin, n_clu), seed
     ((2, 70, 14, 14, 112, 112, 27, 0), 1),         # the linear probe alone
     ((2, 70, 14, 14, 112, 112, 0, 27), 27),        # the cluster probe alone; the skipped slot is untouched
     ((8, 2, 1, 600, 1, 4, 5, 0), 5),               # 150x downsampling at small K: one tile's footprint has 452 columns, more than 256 threads
+    ((2, 32, 15, 17, 121, 135, 12, 16), 0),        # 8 < max(n_lin, n_clu) <= 16: probe_train_kernel<16> (the rows above: <32>, <8>, <64>)
 ]
 
 

@@ -45,7 +45,7 @@ SINGLE = [(48, 3, 96, 144), (40, 5, 80, 80), (48, 3, 48, 48)]         # win, cod
 
 
 @pytest.mark.parametrize("flip", [True, False], ids=["flip", "noflip"])
-@pytest.mark.parametrize("K,n_lin,n_clu", [(70, 27, 29), (16, 3, 3), (128, 64, 64)])
+@pytest.mark.parametrize("K,n_lin,n_clu", [(70, 27, 29), (16, 3, 3), (128, 64, 64), (32, 12, 16)])        # 32, 8, 64 and 16 label slots
 @pytest.mark.parametrize("layout", SINGLE, ids=lambda l: "win%d_code%d_%dx%d" % l)
 def test_single_cover_is_the_probe_head_bitwise(layout, K, n_lin, n_clu, flip):
     from stego_amd import capi
@@ -87,6 +87,7 @@ OVERLAP = [  # win, code side, stride, H, W, K, n_lin, n_clu
     (48, 3, 48, 100, 96, 70, 27, 29),
     (48, 3, 24, 101, 77, 128, 64, 64),      # 64 label slots: one launch per probe
     (48, 3, 24, 101, 77, 16, 3, 3),         # 8 label slots
+    (48, 3, 24, 101, 77, 32, 12, 16),       # 16 label slots: stitch_probe_kernel<16, true, true, PASS_ALL> (27 + 29 above: 32)
 ]
 _cache = {}
 
