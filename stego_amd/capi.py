@@ -1,424 +1,33 @@
-"""ctypes binding of libstego_corr.so (include/stego_corr.h) for torch tensors.
+"""ctypes binding of libstego_corr.so (include/*.h) for torch tensors: the calls.  stego_amd._abi declares the ABI (structures,
+constants, SIGNATURES) and is re-exported here.
 
 This is the ONLY compute backend of stego_amd: there is no PyTorch/CPU fallback.  If the
 library is missing or the tensors are not on a HIP device the calls raise.
 PyTorch is used for device memory (caching allocator), streams and autograd plumbing only.
+
+How a call reaches the library:
+  * _call(name, *args) coerces each argument by the type SIGNATURES gives it.  The one-liners are built on it: NAME_raw =
+    _raw("stego_NAME") hands a launching export out as it is, return code unchecked (tests: the error codes), and the wrappers
+    that take tensors (crf_loss, kmeans_step, ...) check their arguments, allocate and _check() that raw call; _launch_plan,
+    adam_plan, step_stats_plan and aug_check_params use it for their host tables;
+  * NAME_workspace_bytes = _bytes(...) and NAME_desc = _desc(StegoNameDesc) are one-liners of their own helpers;
+  * the per-step wrappers (corr_fwd / corr_bwd, helper_*, head_*, the draws, step_stats_call) and the older wrappers written
+    before _call (the CRF, the data store, sample / dense_corr / knn, the *_plan readers with out-parameters) call lib.stego_*
+    directly with byref() and _ptr().
+A new unit adds its structure, constants and signatures to _abi.py, and here one _raw / _bytes / _desc line per export and the wrapper.
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, byref, c_float, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import Structure, byref, c_float, c_int32, c_int64, c_size_t, c_void_p
 
 import torch
 
 from . import _build
+from ._abi import *  # noqa: F401,F403
+from ._abi import _D, _H, _M, _P, _V  # noqa: F401
 
-ABI_VERSION = 7
-FLAG_SHARED_DEVICE = 1          # StegoCorrDesc.flags
-PREC_F32 = 0
-PREC_F16X3 = 1
-PREC_BF16X3 = PREC_F16X3        # old name of the split mode (it used bf16 halves until round 1, third design)
-
-
-class StegoMap(Structure):
-    _fields_ = [("data", c_void_p), ("stride_n", c_int64), ("stride_c", c_int64),
-                ("stride_h", c_int64), ("stride_w", c_int64)]
-
-
-class StegoCorrDesc(Structure):
-    _fields_ = [("B", c_int32), ("C", c_int32), ("K", c_int32), ("H", c_int32), ("W", c_int32),
-                ("S", c_int32), ("n_neg", c_int32), ("pointwise", c_int32), ("zero_clamp", c_int32),
-                ("stabalize", c_int32), ("pos_intra_shift", c_float), ("pos_inter_shift", c_float),
-                ("neg_inter_shift", c_float), ("precision", c_int32), ("flags", c_int32)]
-
-
-class StegoVitDesc(Structure):
-    """include/stego_vit.h"""
-    _fields_ = [(n, c_int32) for n in ("B", "H", "W", "patch", "D", "depth", "heads", "hidden", "precision")]
-
-
-VIT_F16, VIT_F16X3 = 0, 1
-
-
-class StegoHeadDesc(Structure):
-    """include/stego_head.h"""
-    _fields_ = [("B", c_int32), ("HW", c_int32), ("C", c_int32), ("K", c_int32), ("nonlinear", c_int32),
-                ("tok_stride", c_int64), ("img_stride", c_int64), ("tokens_amax", c_void_p)]
-
-
-class StegoCrfDesc(Structure):
-    """include/stego_crf.h"""
-    _fields_ = [("B", c_int32), ("C", c_int32), ("H", c_int32), ("W", c_int32), ("n_iter", c_int32), ("pos_w", c_float),
-                ("pos_xy_std", c_float), ("bi_w", c_float), ("bi_xy_std", c_float), ("bi_rgb_std", c_float)]
-
-
-CRF_ERR_LIMITS, CRF_ERR_RANGE = 20, 21
-
-
-class StegoDataItem(Structure):
-    """include/stego_data.h: one stored crop of the device image store"""
-    _fields_ = [("img_offset", c_int64), ("label_offset", c_int64)] + \
-        [(n, c_int32) for n in ("h", "w", "nh", "nw", "row_map", "col_map", "center_top", "center_left")]
-
-
-class StegoDataDesc(Structure):
-    """include/stego_data.h"""
-    _fields_ = [("N", c_int32), ("R", c_int32), ("n_items", c_int64), ("img_arena_bytes", c_int64), ("label_arena_bytes", c_int64),
-                ("map_pool_len", c_int64)]
-
-
-DATA_ERR_RES, DATA_ERR_COUNT, DATA_ERR_ITEM, DATA_ERR_RANGE, DATA_ERR_ORIGIN = 30, 31, 32, 33, 34
-DATA_MAX_RES, DATA_MAX_N = 2048, 65535
-
-
-class StegoProbeDesc(Structure):
-    """include/stego_probe.h"""
-    _fields_ = [(n, c_int32) for n in ("B", "K", "h", "w", "H", "W", "n_lin", "n_clu", "lin_kind", "clu_kind")] + [("alpha", c_float)]
-
-
-PROBE_ERR_DIM, PROBE_ERR_SIZE, PROBE_ERR_OUTPUT = 40, 41, 42
-PROBE_SKIP, PROBE_LOG_PROBS, PROBE_PROBS, PROBE_ARGMAX = 0, 1, 2, 3
-PROBE_KINDS = {None: PROBE_SKIP, "log_probs": PROBE_LOG_PROBS, "probs": PROBE_PROBS, "argmax": PROBE_ARGMAX}
-PROBE_MAX_K, PROBE_MAX_N, PROBE_MAX_OUT = 128, 64, 2048
-
-
-class StegoWindowLayout(Structure):
-    """include/stego_stitch.h"""
-    _fields_ = [(n, c_int32) for n in ("H", "W", "win", "stride")]
-
-
-class StegoStitchDesc(Structure):
-    """include/stego_stitch.h"""
-    _fields_ = [("layout", StegoWindowLayout)] + \
-        [(n, c_int32) for n in ("T", "K", "hc", "wc", "n_lin", "n_clu", "lin_kind", "clu_kind")] + [("alpha", c_float)]
-
-
-STITCH_ERR_DIM, STITCH_ERR_SIZE, STITCH_ERR_LAYOUT, STITCH_ERR_WINDOWS, STITCH_ERR_OUTPUT, STITCH_ERR_RANGE = 120, 121, 122, 123, 124, 125
-STITCH_MAX_SIDE = 32768
-
-
-class StegoProbeConfusionDesc(Structure):
-    """include/stego_confusion.h"""
-    _fields_ = [(n, c_int32) for n in ("B", "K", "h", "w", "H", "W", "n_lin", "n_clu", "lin_on", "clu_on")] + \
-        [("alpha", c_float), ("n_classes", c_int32)]
-
-
-class StegoConfusionDesc(Structure):
-    """include/stego_confusion.h"""
-    _fields_ = [(n, c_int32) for n in ("B", "n", "H", "W", "n_classes", "pred_kind")]
-
-
-CONF_ERR_DIM, CONF_ERR_SIZE, CONF_ERR_PROBES, CONF_ERR_KIND = 100, 101, 102, 103
-CONF_LABELS, CONF_SCORES = 0, 1
-CONF_KINDS = {"labels": CONF_LABELS, "scores": CONF_SCORES}
-CONF_MAX_N, CONF_MAX_PIXELS = 64, 1 << 40
-
-
-class StegoPrDesc(Structure):
-    """include/stego_pr.h"""
-    _fields_ = [(n, c_int32) for n in ("B", "C", "h", "w", "HL", "WL", "N1", "N2", "n_bins", "n_classes", "flags")]
-
-
-PR_ERR_DIM, PR_ERR_POINTS, PR_ERR_BINS, PR_ERR_CLASSES, PR_ERR_SIZE, PR_ERR_FLAGS = 50, 51, 52, 53, 54, 55
-PR_RAW, PR_SKIP_UNLABELED = 1, 2
-PR_MAX_C, PR_MAX_POINTS, PR_MIN_BINS, PR_MAX_BINS, PR_MAX_CLASSES, PR_MAX_SIDE = 768, 4096, 64, 8192, 255, 16384
-
-
-class StegoProbeTrainDesc(Structure):
-    """include/stego_probe_train.h"""
-    _fields_ = [(n, c_int32) for n in ("B", "K", "h", "w", "H", "W", "n_lin", "n_clu")]
-
-
-PTRAIN_ERR_DIM, PTRAIN_ERR_SIZE, PTRAIN_ERR_PROBES = 60, 61, 62
-PTRAIN_MAX_K, PTRAIN_MAX_N, PTRAIN_MAX_OUT, PTRAIN_MAX_CODE = 128, 64, 2048, 65535
-
-
-class StegoHeatDesc(Structure):
-    """include/stego_heat.h"""
-    _fields_ = [(n, c_int32) for n in ("B", "C", "hs", "ws", "h", "w", "N", "H", "W", "flags")]
-
-
-HEAT_ERR_DIM, HEAT_ERR_POINTS, HEAT_ERR_SIZE, HEAT_ERR_OUTPUT, HEAT_ERR_FLAGS = 70, 71, 72, 73, 74
-HEAT_NO_CENTER, HEAT_NO_CLAMP = 1, 2
-HEAT_MAX_C, HEAT_MAX_POINTS, HEAT_MAX_SIDE, HEAT_MAX_CELLS, HEAT_MAX_OUT = 768, 4096, 16384, 16384, 2048
-
-
-class StegoCrfLossDesc(Structure):
-    """include/stego_crf_loss.h"""
-    _fields_ = [(n, c_int32) for n in ("B", "K", "G", "h", "w", "hg", "wg", "H", "W", "N")] + \
-               [(n, c_float) for n in ("alpha", "beta", "gamma", "w1", "w2", "shift")] + [("flags", c_int32)]
-
-
-CRFLOSS_ERR_DIM, CRFLOSS_ERR_POINTS, CRFLOSS_ERR_SIZE, CRFLOSS_ERR_PARAM, CRFLOSS_ERR_FLAGS = 80, 81, 82, 83, 84
-CRFLOSS_NORMALIZE = 1
-CRFLOSS_MAX_K, CRFLOSS_MAX_G, CRFLOSS_MAX_POINTS, CRFLOSS_MAX_SIDE, CRFLOSS_LAUNCHES = 128, 8, 4096, 2048, 3
-
-
-class StegoAugParams(Structure):
-    """include/stego_aug.h: one image's draws (64 bytes)"""
-    _fields_ = [(n, c_int32) for n in ("flip", "top", "left", "ch", "cw")] + [("order", c_int32 * 4), ("factor", c_float * 4),
-                                                                              ("gray", c_int32), ("blur_sigma", c_float), ("reserved", c_int32)]
-
-
-class StegoAugDesc(Structure):
-    """include/stego_aug.h"""
-    _fields_ = [(n, c_int32) for n in ("B", "H", "W", "R")]
-
-
-class StegoAugAlignDesc(Structure):
-    """include/stego_aug.h"""
-    _fields_ = [(n, c_int32) for n in ("B", "K", "h", "w", "S", "Rh", "Rw")]
-
-
-AUG_ERR_SIZE, AUG_ERR_PARAM, AUGALIGN_ERR_DIM, AUGALIGN_ERR_SIZE = 90, 91, 92, 93
-AUG_BRIGHTNESS, AUG_CONTRAST, AUG_SATURATION, AUG_HUE, AUG_NONE = 0, 1, 2, 3, 4
-AUG_MAX_SIDE, AUG_MIN_RES, AUG_LAUNCHES, AUGALIGN_MAX_K, AUGALIGN_MAX_SIDE, AUGALIGN_LAUNCHES = 2048, 3, 2, 128, 256, 2
-
-
-class StegoAdamSegment(Structure):
-    """include/stego_optim.h: one record of the segment table (40 bytes)"""
-    _fields_ = [("param", c_void_p), ("count", c_int64), ("grad_offset", c_int64), ("state_offset", c_int64), ("group", c_int32),
-                ("reserved", c_int32)]
-
-
-class StegoAdamGroup(Structure):
-    """include/stego_optim.h"""
-    _fields_ = [(n, ctypes.c_double) for n in ("lr", "beta1", "beta2", "eps")] + [("active", c_int32), ("reserved", c_int32)]
-
-
-OPTIM_ERR_COUNT, OPTIM_ERR_SEGMENT, OPTIM_ERR_PARAM, OPTIM_ERR_FLAGS = 110, 111, 112, 113
-ADAM_MAX_SEGMENTS, ADAM_MAX_GROUPS, ADAM_MAX_ELEMS, ADAM_CHUNK, ADAM_MAX_GRID = 256, 8, 1 << 31, 1024, 2048
-
-
-class StegoAdamDesc(Structure):
-    """include/stego_optim.h"""
-    _fields_ = [(n, c_int32) for n in ("n_segments", "n_groups", "zero_grads", "reserved")] + \
-        [("grad_elems", c_int64), ("state_elems", c_int64), ("groups", StegoAdamGroup * ADAM_MAX_GROUPS)]
-
-
-class StegoStatsDesc(Structure):
-    """include/stego_stats.h"""
-    _fields_ = [("n_tensors", c_int32), ("n_scalars", c_int32), ("with_hist", c_int32), ("ring_slots", c_int32), ("counts", c_int64 * 4)]
-
-
-STATS_PLAN_FIELDS = ("grid", "chunk", "record_bytes", "off_step", "off_with_hist", "off_n_tensors", "off_tensors", "tensor_stride",
-                     "t_n_finite", "t_n_nan", "t_n_out", "t_sum", "t_sum_sq", "t_min", "t_max", "off_scalars", "off_hist", "hist_stride",
-                     "ring_bytes", "state_bytes", "workspace_bytes")
-
-
-class StegoStatsPlan(Structure):
-    """include/stego_stats.h: the launch and the record layout (byte offsets)"""
-    _fields_ = [(name, c_int64) for name in STATS_PLAN_FIELDS]
-
-
-STATS_ERR_COUNT, STATS_ERR_RING, STATS_ERR_FLAGS = 160, 161, 162
-STATS_MAX_TENSORS, STATS_MAX_SCALARS, STATS_MAX_ELEMS, STATS_MAX_SLOTS, STATS_BUCKETS, STATS_LIMITS = 4, 16, 1 << 31, 65536, 1548, 1549
-
-
-class StegoSalienceDesc(Structure):
-    """include/stego_salience.h"""
-    _fields_ = [(n, c_int32) for n in ("B", "H", "W", "S", "mask_dtype")]
-
-
-SALIENCE_ERR_SIZE, SALIENCE_ERR_SAMPLES, SALIENCE_ERR_DTYPE = 130, 131, 132
-SALIENCE_U8, SALIENCE_F32 = 0, 1
-SALIENCE_MAX_PIXELS, SALIENCE_MAX_S, SALIENCE_MAX_B = 1 << 20, 16, 65535
-
-
-class StegoRecDesc(Structure):
-    """include/stego_rec.h"""
-    _fields_ = [(n, c_int32) for n in ("B", "K", "C", "h", "w")]
-
-
-REC_ERR_DIM, REC_ERR_SIZE = 140, 141
-REC_MAX_K, REC_MAX_C, REC_MAX_B, REC_MAX_SIDE, REC_MAX_TOKENS = 128, 1024, 65535, 2048, 1 << 24
-REC_TILE, REC_MAX_WORKGROUPS, REC_LAUNCHES = 32, 64, 2
-
-class StegoRenderDesc(Structure):
-    """include/stego_render.h"""
-    _fields_ = [(n, c_int32) for n in ("B", "H", "W", "n_lut", "label_dtype", "flags")] + \
-        [("alpha", c_float), ("mean", c_float * 3), ("std", c_float * 3), ("ignore_rgb", ctypes.c_uint8 * 4), ("edge_rgb", ctypes.c_uint8 * 4)] + \
-        [(n, c_int64) for n in ("label_stride_n", "label_stride_h", "label_stride_w", "out_stride_n", "out_stride_h")]
-
-
-RENDER_ERR_SIZE, RENDER_ERR_LUT, RENDER_ERR_DTYPE, RENDER_ERR_FLAGS, RENDER_ERR_PARAM, RENDER_ERR_SELECT = 150, 151, 152, 153, 154, 155
-RENDER_IMAGE, RENDER_LABELS, RENDER_EDGES, RENDER_BLEND, RENDER_RESCALE = 1, 2, 4, 8, 16
-RENDER_I64, RENDER_I32, RENDER_U8 = 0, 1, 2
 RENDER_DTYPES = {torch.int64: RENDER_I64, torch.int32: RENDER_I32, torch.uint8: RENDER_U8}
-RENDER_MAX_LUT, RENDER_MAX_B = 512, 65535
-
-
-class StegoPcaDesc(Structure):
-    """include/stego_pca.h"""
-    _fields_ = [(n, c_int32) for n in ("B", "C", "h", "w", "H", "W", "group", "n_iter", "resize", "scale")] + \
-        [(n, c_int64) for n in ("out_stride_n", "out_stride_h")]
-
-
-PCA_ERR_DIM, PCA_ERR_SIZE, PCA_ERR_ITER, PCA_ERR_MODE = 170, 171, 172, 173
-PCA_PER_IMAGE, PCA_JOINT = 0, 1
-PCA_BILINEAR, PCA_NEAREST = 0, 1
-PCA_UNIT, PCA_RANGE = 0, 1
-PCA_RESIZES = {"bilinear": PCA_BILINEAR, "nearest": PCA_NEAREST}
-PCA_SCALES = {"unit": PCA_UNIT, "range": PCA_RANGE}
-PCA_MIN_C, PCA_MAX_C, PCA_MAX_B, PCA_MAX_SIDE, PCA_MAX_TOKENS, PCA_MIN_TOKENS = 3, 768, 65535, 4096, 1 << 28, 4
-PCA_MAX_ITER, PCA_DEFAULT_ITER, PCA_FOLD = 256, 32, 1024
-
-
-class StegoKmeansDesc(Structure):
-    """include/stego_kmeans.h"""
-    _fields_ = [(n, c_int32) for n in ("B", "K", "h", "w", "n")]
-
-
-KMEANS_ERR_DIM, KMEANS_ERR_SIZE, KMEANS_ERR_DRAW = 180, 181, 182
-KMEANS_MAX_K, KMEANS_MAX_N, KMEANS_MAX_B, KMEANS_MAX_TOKENS = 128, 64, 65535, (1 << 31) - 1
-KMEANS_FOLD, KMEANS_TILE, KMEANS_MAX_WORKGROUPS = 1024, 128, 512
-
-
-class StegoRegionsDesc(Structure):
-    """include/stego_regions.h"""
-    _fields_ = [(n, c_int32) for n in ("B", "H", "W", "connectivity", "label_dtype")]
-
-
-REGIONS_ERR_SIZE, REGIONS_ERR_CONN, REGIONS_ERR_DTYPE, REGIONS_ERR_LABELS, REGIONS_ERR_RANGE = 190, 191, 192, 193, 194
-REGIONS_I64, REGIONS_I32, REGIONS_U8 = 0, 1, 2
 REGIONS_DTYPES = {torch.int64: REGIONS_I64, torch.int32: REGIONS_I32, torch.uint8: REGIONS_U8}
-REGIONS_TILE, REGIONS_CHUNK, REGIONS_MAX_LABELS, REGIONS_LAUNCHES, REGIONS_MAX_B, REGIONS_MAX_PIXELS = 32, 2048, 256, 6, 65535, (1 << 31) - 1
-REGIONS_COLS32 = ("area", "y0", "x0", "y1", "x1", "first")
-REGIONS_COLS64 = ("label", "sum_y", "sum_x")
-
-class StegoRegionPoolDesc(Structure):
-    """include/stego_region_pool.h"""
-    _fields_ = [(n, c_int32) for n in ("B", "C", "h", "w", "H", "W")] + [("rows", c_int64)]
-
-
-REGION_POOL_ERR_SIZE, REGION_POOL_ERR_DIM, REGION_POOL_ERR_RANGE = 200, 201, 202
-REGION_POOL_MAX_C, REGION_POOL_CB, REGION_POOL_PARTIALS, REGION_POOL_LAUNCHES = 2048, 128, 1024, 3
-
-# name -> (restype, argtypes); every symbol include/stego_corr.h declares
-_P = c_void_p
-_H = POINTER(StegoHeadDesc)
-_D = POINTER(StegoCorrDesc)
-_M = POINTER(StegoMap)
-_V = POINTER(StegoVitDesc)
-SIGNATURES = {
-    "stego_vit_param_count": (c_int32, [_V]),
-    "stego_vit_weights_bytes": (c_size_t, [_V]),
-    "stego_vit_workspace_bytes": (c_size_t, [_V]),
-    "stego_vit_pack_weights": (c_int32, [_V, POINTER(ctypes.c_void_p), c_int32, _P, c_size_t, _P]),
-    "stego_vit_forward": (c_int32, [_V, _P, _P, _P, _P, c_size_t, _P]),
-    "stego_vit_forward_keys": (c_int32, [_V, _P, _P, _P, _P, c_size_t, _P]),
-    "stego_vit_forward_attn": (c_int32, [_V, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "stego_attn_salience": (c_int32, [_P] + [c_int32] * 5 + [c_float, _P, _P, _P]),
-    "stego_head_fwd_workspace_bytes": (c_size_t, [_H]),
-    "stego_head_bwd_workspace_bytes": (c_size_t, [_H]),
-    "stego_head_fwd": (c_int32, [_H] + [_P] * 10 + [_P] * 3 + [_P, c_size_t, _P]),
-    "stego_head_bwd": (c_int32, [_H] + [_P] * 6 + [_P] * 6 + [_P, c_size_t, _P]),
-    "stego_crf_workspace_bytes": (c_size_t, [POINTER(StegoCrfDesc)]),
-    "stego_crf_run": (c_int32, [POINTER(StegoCrfDesc), _P, _P, _P, _P, c_size_t, _P]),
-    "stego_crf_lattice_info": (c_int32, [POINTER(StegoCrfDesc), _P, c_size_t, c_int32, c_int32, POINTER(c_int32), _P, c_int32, _P]),
-    "stego_data_check_items": (c_int32, [POINTER(StegoDataDesc), _P, POINTER(c_int64)]),
-    "stego_data_prepare": (c_int32, [POINTER(StegoDataDesc)] + [_P] * 10 + [_P]),
-    "stego_data_prepare_dir": (c_int32, [POINTER(StegoDataDesc)] + [_P] * 10 + [_P]),
-    "stego_salience_coords": (c_int32, [POINTER(StegoSalienceDesc)] + [_P] * 8 + [_P]),
-    "stego_probe_head": (c_int32, [POINTER(StegoProbeDesc), _M, _M] + [_P] * 5 + [_P]),
-    "stego_probe_head_plan": (c_size_t, [POINTER(StegoProbeDesc), POINTER(c_int32), POINTER(c_int32)]),
-    "stego_stitch_probe": (c_int32, [POINTER(StegoStitchDesc), _M, _M] + [_P] * 5 + [_P]),
-    "stego_stitch_probe_plan": (c_size_t, [POINTER(StegoStitchDesc)] + [POINTER(c_int32)] * 4),
-    "stego_window_gather": (c_int32, [POINTER(StegoWindowLayout), _M, c_int32, c_int32, _P, _P, _P]),
-    "stego_image_range_workspace_bytes": (c_size_t, [POINTER(StegoRenderDesc)]),
-    "stego_image_range": (c_int32, [POINTER(StegoRenderDesc), _M, _P, _P, c_size_t, _P]),
-    "stego_render": (c_int32, [POINTER(StegoRenderDesc), _M, _P, _P, _P, _P, _P]),
-    "stego_pca_workspace_bytes": (c_size_t, [POINTER(StegoPcaDesc)]),
-    "stego_pca_fit": (c_int32, [POINTER(StegoPcaDesc), _M, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "stego_pca_scores": (c_int32, [POINTER(StegoPcaDesc), _M, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "stego_pca_paint": (c_int32, [POINTER(StegoPcaDesc), _P, _P, _P, _P]),
-    "stego_kmeans_workspace_bytes": (c_size_t, [POINTER(StegoKmeansDesc)]),
-    "stego_kmeans_plan": (c_size_t, [POINTER(StegoKmeansDesc), POINTER(c_int32)]),
-    "stego_kmeans_step": (c_int32, [POINTER(StegoKmeansDesc), _M, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "stego_kmeans_seed": (c_int32, [POINTER(StegoKmeansDesc), _M, _P, _P, _P, _P, c_size_t, _P]),
-    "stego_regions_workspace_bytes": (c_size_t, [POINTER(StegoRegionsDesc)]),
-    "stego_regions_plan": (c_int32, [POINTER(StegoRegionsDesc), POINTER(c_int32), POINTER(c_size_t), POINTER(c_int64)]),
-    "stego_regions_label": (c_int32, [POINTER(StegoRegionsDesc), _P, _P, _P, _P, _P, c_size_t, _P]),
-    "stego_regions_table": (c_int32, [POINTER(StegoRegionsDesc), _P, _P, _P, c_int64, _P, _P, _P]),
-    "stego_regions_votes": (c_int32, [POINTER(StegoRegionsDesc), _P, _P, _P, c_int64, _P, c_int64, c_int64, c_int32, _P, _P]),
-    "stego_regions_relabel": (c_int32, [POINTER(StegoRegionsDesc), _P, _P, _P, _P, c_int64, _P, _P, c_int64, c_int64, c_int32, _P, _P, _P]),
-    "stego_region_pool_workspace_bytes": (c_size_t, [POINTER(StegoRegionPoolDesc)]),
-    "stego_region_pool_plan": (c_int32, [POINTER(StegoRegionPoolDesc), POINTER(c_int32), POINTER(c_int32), POINTER(c_size_t), POINTER(c_int64)]),
-    "stego_region_pool": (c_int32, [POINTER(StegoRegionPoolDesc), _M, _P, _P, _P, c_int64, c_int64, c_int64, _P, _P, c_size_t, _P]),
-    "stego_probe_confusion": (c_int32, [POINTER(StegoProbeConfusionDesc), _M, _M] + [_P] * 6 + [_P]),
-    "stego_probe_confusion_plan": (c_size_t, [POINTER(StegoProbeConfusionDesc), POINTER(c_int32), POINTER(c_int32)]),
-    "stego_confusion": (c_int32, [POINTER(StegoConfusionDesc), _P, _P, _P, _P]),
-    "stego_adam_step": (c_int32, [POINTER(StegoAdamDesc), _P, _P, _P, _P, _P, _P, _P, _P]),
-    "stego_adam_plan": (c_int32, [POINTER(StegoAdamDesc), _P, POINTER(c_int32), POINTER(c_int32), POINTER(c_int64)]),
-    "stego_step_stats": (c_int32, [POINTER(StegoStatsDesc), _P, _P, _P, _P, _P, _P]),
-    "stego_step_stats_plan": (c_int32, [POINTER(StegoStatsDesc), POINTER(StegoStatsPlan)]),
-    "stego_step_stats_edges": (c_int32, [_P, _P]),
-    "stego_pr_accumulate": (c_int32, [POINTER(StegoPrDesc), _M, _M] + [_P] * 6 + [_P]),
-    "stego_pr_plan": (c_size_t, [POINTER(StegoPrDesc), POINTER(c_int32), POINTER(c_int32)]),
-    "stego_probe_train_workspace_bytes": (c_size_t, [POINTER(StegoProbeTrainDesc)]),
-    "stego_probe_train": (c_int32, [POINTER(StegoProbeTrainDesc), _M] + [_P] * 9 + [_P, c_size_t, _P]),
-    "stego_probe_train_plan": (c_size_t, [POINTER(StegoProbeTrainDesc), POINTER(c_int32)]),
-    "stego_heat_workspace_bytes": (c_size_t, [POINTER(StegoHeatDesc)]),
-    "stego_heat_plan": (c_size_t, [POINTER(StegoHeatDesc), POINTER(c_int32), POINTER(c_int32), POINTER(c_size_t), POINTER(c_int32)]),
-    "stego_corr_heatmaps": (c_int32, [POINTER(StegoHeatDesc), _M, _M] + [_P] * 5 + [_P, c_size_t, _P]),
-    "stego_crf_loss_workspace_bytes": (c_size_t, [POINTER(StegoCrfLossDesc)]),
-    "stego_crf_loss_plan": (c_int32, [POINTER(StegoCrfLossDesc), POINTER(c_size_t), POINTER(c_int64)]),
-    "stego_crf_loss": (c_int32, [POINTER(StegoCrfLossDesc), _M, _M, _P, _P, _P, _M, _P, c_size_t, _P]),
-    "stego_augment_check_params": (c_int32, [POINTER(StegoAugDesc), _P, POINTER(c_int64), POINTER(c_int32)]),
-    "stego_augment_workspace_bytes": (c_size_t, [POINTER(StegoAugDesc)]),
-    "stego_augment_plan": (c_int32, [POINTER(StegoAugDesc), POINTER(c_size_t), POINTER(c_int64)]),
-    "stego_augment": (c_int32, [POINTER(StegoAugDesc), _M, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "stego_aug_align_workspace_bytes": (c_size_t, [POINTER(StegoAugAlignDesc)]),
-    "stego_aug_align_plan": (c_int32, [POINTER(StegoAugAlignDesc), POINTER(c_size_t), POINTER(c_int64)]),
-    "stego_aug_align": (c_int32, [POINTER(StegoAugAlignDesc), _M, _M, _P, _P, _M, _M, _P, c_size_t, _P]),
-    "stego_rec_loss_workspace_bytes": (c_size_t, [POINTER(StegoRecDesc)]),
-    "stego_rec_loss_plan": (c_int32, [POINTER(StegoRecDesc), POINTER(c_size_t), POINTER(c_int64)]),
-    "stego_rec_loss": (c_int32, [POINTER(StegoRecDesc), _M, _M, _P, _P, _P, _M, _P, _P, _P, c_size_t, _P]),
-    "stego_abi_version": (c_int32, []),
-    "stego_debug_set": (c_int32, [c_int32, c_int32]),
-    "stego_debug_occupy": (c_int32, [c_int32, c_int32, c_int32, _P]),
-    "stego_error_string": (ctypes.c_char_p, [c_int32]),
-    "stego_corr_workspace_bytes": (c_size_t, [_D]),
-    "stego_corr_saved_ctx_bytes": (c_size_t, [_D]),
-    "stego_corr_helper_workspace_bytes": (c_size_t, [_D]),
-    "stego_corr_helper_saved_ctx_bytes": (c_size_t, [_D]),
-    "stego_dense_corr_workspace_bytes": (c_size_t, [c_int32] * 6),
-    "stego_dense_corr": (c_int32, [_M, _M] + [c_int32] * 7 + [_P, _P, c_size_t, _P]),
-    "stego_dense_corr_kernel": (c_int32, [_M, _M] + [c_int32] * 6),
-    "stego_sample": (c_int32, [_M, _P, c_int32, c_int32, c_int32, c_int32, _P, c_int32, c_int32, _P, _P]),
-    "stego_sample_bwd": (c_int32, [_P, _M, _P, c_int32, c_int32, c_int32, c_int32, _P, c_int32, c_int32, _P]),
-    "stego_sample_bwd_rows": (c_int32, [_P, _P, _P, _M, _P, c_int32, c_int32, c_int32, c_int32, _P, c_int32, c_int32, _P]),
-    "stego_panel_image_bytes": (c_size_t, [c_int32, c_int32]),
-    "stego_sample_panels": (c_int32, [_M, _P, c_int32, c_int32, c_int32, c_int32, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P]),
-    "stego_dense_corr_panels": (c_int32, [_P, _P, c_int32, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P]),
-    "stego_rowsum": (c_int32, [_P, ctypes.c_int64, c_int32, _P, _P]),
-    "stego_loss_pointwise_fwd": (c_int32, [_P] * 4 + [c_int32] * 3 + [POINTER(c_float), c_float, c_float, c_int32, _P, _P, _P]),
-    "stego_loss_pointwise_bwd": (c_int32, [_P] * 4 + [c_int32] * 3 + [POINTER(c_float), c_float, c_float, c_int32, _P, _P, _P, _P, _P]),
-    "stego_knn_workspace_bytes": (c_size_t, [ctypes.c_int64, c_int32, c_int32, ctypes.c_int64]),
-    "stego_knn_topk": (c_int32, [_P, ctypes.c_int64, c_int32, ctypes.c_int64, c_int32, c_int32, ctypes.c_int64, ctypes.c_int64,
-                                 _P, _P, _P, c_size_t, _P]),
-    "stego_corr_fwd": (c_int32, [_D] + [_M] * 4 + [_P] * 3 + [_P] * 8 + [_P, c_size_t, _P]),
-    "stego_corr_fwd_prepared": (c_int32, [_D] + [_M] * 4 + [_P] * 3 + [_P] * 8 + [_P, c_size_t, _P]),
-    "stego_corr_workspace_prepare": (c_int32, [_D, _P, c_size_t, _P]),
-    "stego_corr_workspace_prepare_now": (c_int32, [_D, _P, c_size_t]),
-    "stego_corr_fwd_launches": (c_int32, [_D] + [_M] * 4),
-    "stego_corr_event_counters": (c_void_p, [_D, _P, c_size_t]),
-    "stego_ref_draws": (c_int32, [ctypes.c_uint64, ctypes.c_uint64, c_int32, c_int64, c_int32, c_int32, _P, _P, _P, _P]),
-    "stego_ref_draws_advance": (ctypes.c_uint64, [c_int64, c_int32, c_int32, c_int32]),
-    "stego_tokens_from_cache": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P]),
-    "stego_ref_dropout_masks": (c_int32, [ctypes.c_uint64, ctypes.c_uint64, _P, _P, c_int32, c_int32, c_int64, c_float, _P, _P]),
-    "stego_ref_dropout_masks_advance": (ctypes.c_uint64, [c_int64, c_int32, c_int32]),
-    "stego_ref_draws_indirect": (c_int32, [_P, _P, ctypes.c_uint64, c_int32, c_int64, c_int32, c_int32, _P, _P, _P, _P]),
-    "stego_fast_draws": (c_int32, [_P, ctypes.c_int64, c_int32, c_int32, _P, _P, _P, _P]),
-    "stego_finish_draws": (c_int32, [_P, _P, ctypes.c_int64, POINTER(ctypes.c_void_p), c_int32, c_int32, _P, _P, _P, _P]),
-    "stego_corr_fwd_profile": (c_int32, [_D] + [_M] * 4 + [_P] * 3 + [_P] * 8 + [_P, c_size_t, _P]
-                               + [c_int32, POINTER(c_float)]),
-    "stego_corr_bwd_workspace_bytes": (c_size_t, [_D]),
-    "stego_corr_helper_bwd_workspace_bytes": (c_size_t, [_D]),
-    "stego_corr_bwd": (c_int32, [_D] + [_P] + [_P] * 3 + [_P] * 3 + [_P, _P, _P, c_int32] + [_P] * 3
-                       + [_P, _P] + [_P, c_size_t, _P]),
-    "stego_corr_helper_fwd": (c_int32, [_D] + [_M] * 4 + [_P] * 5 + [_P, c_size_t, _P]),
-    "stego_corr_helper_bwd": (c_int32, [_D] + [_P] * 6 + [_P, _P] + [_P, c_size_t, _P]),
-}
 
 _lib = None
 
@@ -443,6 +52,7 @@ def load():
         fn = getattr(lib, name)     # AttributeError if the .so is stale / symbol missing
         fn.restype = res
         fn.argtypes = args
+        _CALLS[name] = (fn, len(args), tuple((i, c) for i, c in enumerate(map(_converter, args)) if c is not None))
     if lib.stego_abi_version() != ABI_VERSION:
         raise RuntimeError("stego_amd: ABI version mismatch, rebuild the library")
     _lib = lib
@@ -500,23 +110,112 @@ def _ptr(t):
 
 
 def _addr(x):
-    """A tensor's address; a raw address or None as it is (the *_raw wrappers: tests hand them NULL and misaligned pointers)."""
-    return _ptr(x) if torch.is_tensor(x) else x
+    """What a void* argument takes: a tensor's address, a structure's address; a raw address or None as it is (tests hand the *_raw
+    functions NULL and misaligned pointers), and so a ctypes array (a host table), whose address ctypes passes itself."""
+    if x is None:
+        return x
+    if torch.is_tensor(x):
+        return x.data_ptr()
+    return ctypes.addressof(x) if isinstance(x, Structure) else x
 
 
-def _ref(m):
-    """byref of a StegoMap, or NULL."""
-    return byref(m) if m is not None else None
+def _converter(ctype):
+    """What _call does to an argument that SIGNATURES declares as `ctype`; None: nothing."""
+    if ctype is c_void_p:
+        return _addr
+    if issubclass(ctype, ctypes._Pointer):
+        # POINTER(StegoX): ctypes itself passes a StegoX instance by reference and None as NULL; out-parameters and arrays
+        # (POINTER(c_int32), ...) go as given
+        return None
+    return float if ctype in (c_float, ctypes.c_double) else int
 
 
-_desc_ref = _ref        # ... of a descriptor or a window layout, or NULL
+_CALLS = {}     # export -> (the C function, its argument count, ((position, converter) of every argument that has one)), filled by load()
 
 
-def _launch_plan(fn, desc, n):
+def _call(name, *args):
+    """The export `name` on arguments as Python has them: a structure or None where it takes one by reference, a tensor, a ctypes
+    array, an address or None where it takes a pointer, numbers as they come.  -> the return code (or byte count) as an int,
+    unchecked."""
+    if _lib is None:
+        load()
+    fn, n, convert = _CALLS[name]
+    if len(args) != n:
+        raise TypeError("%s takes %d arguments, got %d" % (name, n, len(args)))
+    args = list(args)
+    for i, c in convert:
+        if args[i].__class__ is not int:        # (ctypes takes an int as it is for every scalar and pointer type: most arguments)
+            args[i] = c(args[i])
+    return int(fn(*args))
+
+
+def _raw(name):
+    """NAME_raw = _raw("stego_NAME"), for an export whose last parameter is the stream: the export with every argument given, in the
+    header's order (maps as StegoMap or None, the rest tensors, raw addresses or None; `stream` last, by name, or left out: NULL) ->
+    the return code, unchecked."""
+    n = len(SIGNATURES[name][1])
+
+    def raw(*args, stream=None):
+        return _call(name, *args, stream) if len(args) == n - 1 else _call(name, *args)
+    return raw
+
+
+def _bytes(name):
+    """NAME_workspace_bytes = _bytes("stego_NAME_workspace_bytes") (host only) -> the bytes; 0 for an invalid descriptor."""
+    def workspace_bytes(desc):
+        return int(getattr(_lib or load(), name)(desc))
+    return workspace_bytes
+
+
+def _desc(cls, **defaults):
+    """NAME_desc = _desc(StegoNameDesc, flags=0): a descriptor from its fields in the structure's order, by position or by name, each
+    coerced to its C type (int / float); `defaults` for trailing fields."""
+    names = tuple(n for n, _ in cls._fields_)
+    coerce = tuple(float if t in (c_float, ctypes.c_double) else int for _, t in cls._fields_)
+
+    def make(*args, **kw):
+        if not kw and len(args) == len(names):
+            try:
+                return cls(*args)       # every value already of its field's kind (the per-step callers): ctypes takes them as they are
+            except TypeError:           # e.g. a float for an integer field: coerced below, as int() does
+                pass
+        else:
+            given = dict(defaults, **dict(zip(names, args)), **kw)      # (a field given twice is dict()'s TypeError)
+            if len(args) > len(names) or set(given) != set(names):
+                raise TypeError("%s takes (%s), got %d values and %s" % (cls.__name__, ", ".join(names), len(args), sorted(kw)))
+            args = [given[k] for k in names]
+        return cls(*[c(a) for c, a in zip(coerce, args)])
+    return make
+
+
+def _workspace_need(workspace_bytes, desc, reject):
+    """The workspace bytes `desc` needs, from the unit's NAME_workspace_bytes.  0 bytes = an invalid descriptor: reject() - the unit's
+    host-only plan where it has one, else the entry point without buffers - names the error and _check raises it before any output
+    is sized from the descriptor."""
+    need = workspace_bytes(desc)
+    if need == 0:
+        _check(reject())
+    return need
+
+
+def _workspace(workspace_bytes, desc, dev, reject):
+    """(a fresh workspace tensor, its bytes) for `desc`; an invalid descriptor raises as in _workspace_need."""
+    need = _workspace_need(workspace_bytes, desc, reject)
+    return _empty_bytes(need, dev), need
+
+
+def _expect(who, name, t, dtype, shape):
+    """Raise unless `t` is a contiguous tensor of this dtype and shape (None: any extent)."""
+    if t.dtype != dtype or t.dim() != len(shape) or not t.is_contiguous() or any(s is not None and s != n for s, n in zip(shape, t.shape)):
+        raise RuntimeError("%s: %s must be a contiguous %s tensor of shape %s, got %s %s"
+                           % (who, name, dtype, tuple(shape), t.dtype, tuple(t.shape)))
+
+
+def _launch_plan(name, desc, n):
     """An array-style stego_*_plan export (host only) -> (return code, [(LDS bytes, workgroups) of each of the n launches])."""
     lds, wgs = (c_size_t * n)(), (c_int64 * n)()
-    rc = fn(byref(desc), lds, wgs)
-    return int(rc), [(int(a), int(b)) for a, b in zip(lds, wgs)]
+    rc = _call(name, desc, lds, wgs)
+    return rc, [(int(a), int(b)) for a, b in zip(lds, wgs)]
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -1211,14 +910,9 @@ def head_bwd(tokens, masks, saved_h, w22, d_code, K):
     return dw1, db1, dw21, db21, dw22, db22
 
 
-def crf_desc(B, C, H, W, n_iter, pos_w, pos_xy_std, bi_w, bi_xy_std, bi_rgb_std):
-    return StegoCrfDesc(int(B), int(C), int(H), int(W), int(n_iter), float(pos_w), float(pos_xy_std), float(bi_w), float(bi_xy_std),
-                        float(bi_rgb_std))
-
-
-def crf_workspace_bytes(desc):
-    """stego_crf_workspace_bytes (host only; 0 = invalid descriptor)."""
-    return int(load().stego_crf_workspace_bytes(byref(desc)))
+# (every NAME_workspace_bytes below: host only, 0 for an invalid descriptor)
+crf_desc = _desc(StegoCrfDesc)
+crf_workspace_bytes = _bytes("stego_crf_workspace_bytes")
 
 
 def crf_run(desc, bgr_u8, probs, keep_workspace=False, workspace=None):
@@ -1249,8 +943,7 @@ def crf_lattice_info(desc, ws, b, which, max_keys=0):
 
 
 # ---- batch preparation of the device image store (include/stego_data.h; stego_amd.device_data builds the table and the arenas)
-def data_desc(N, R, n_items, img_arena_bytes, label_arena_bytes, map_pool_len):
-    return StegoDataDesc(int(N), int(R), int(n_items), int(img_arena_bytes), int(label_arena_bytes), int(map_pool_len))
+data_desc = _desc(StegoDataDesc)
 
 
 def data_check_items(desc, items_np):
@@ -1338,8 +1031,8 @@ def salience_coords(mask1, mask2, u, u_mix, reg1, reg2):
 
 
 # ---- fused probe head (include/stego_probe.h; stego_amd.segment wraps it for a model)
-def probe_desc(B, K, h, w, H, W, n_lin, n_clu, lin_kind, clu_kind, alpha):
-    return StegoProbeDesc(int(B), int(K), int(h), int(w), int(H), int(W), int(n_lin), int(n_clu), int(lin_kind), int(clu_kind), float(alpha))
+probe_desc = _desc(StegoProbeDesc)
+probe_head_raw = _raw("stego_probe_head")
 
 
 def probe_head_plan(desc):
@@ -1347,14 +1040,6 @@ def probe_head_plan(desc):
     ty, tx = c_int32(0), c_int32(0)
     n = load().stego_probe_head_plan(byref(desc), byref(ty), byref(tx))
     return int(n), ty.value, tx.value
-
-
-def probe_head_raw(desc, code, code_flip, lin_w, lin_b, centroids, lin_out, clu_out, stream=None):
-    """stego_probe_head with every argument given: `code` / `code_flip` are StegoMap (or None), the rest raw addresses or tensors
-    (tests: the error codes) -> the return code, unchecked."""
-    return int(load().stego_probe_head(byref(desc), _ref(code),
-                                       _ref(code_flip), _addr(lin_w), _addr(lin_b), _addr(centroids),
-                                       _addr(lin_out), _addr(clu_out), stream if stream is not None else None))
 
 
 def _probe_weights(lin_w, lin_b, centroids, n_lin, n_clu, K):
@@ -1399,8 +1084,9 @@ def probe_head(code, code_flip, lin_w, lin_b, centroids, size, lin_kind, clu_kin
 
 
 # ---- sliding windows stitched on the canvas (include/stego_stitch.h; stego_amd.segment.segment_large wraps them for a model)
-def window_layout(H, W, win, stride):
-    return StegoWindowLayout(int(H), int(W), int(win), int(stride))
+window_layout = _desc(StegoWindowLayout)
+stitch_probe_raw = _raw("stego_stitch_probe")
+window_gather_raw = _raw("stego_window_gather")
 
 
 def stitch_desc(H, W, win, stride, T, K, hc, wc, n_lin, n_clu, lin_kind, clu_kind, alpha):
@@ -1413,14 +1099,6 @@ def stitch_probe_plan(desc):
     ty, tx, ny, nx = c_int32(0), c_int32(0), c_int32(0), c_int32(0)
     n = load().stego_stitch_probe_plan(byref(desc), byref(ty), byref(tx), byref(ny), byref(nx))
     return int(n), ty.value, tx.value, ny.value, nx.value
-
-
-def stitch_probe_raw(desc, code, code_flip, lin_w, lin_b, centroids, lin_out, clu_out, stream=None):
-    """stego_stitch_probe with every argument given: `code` / `code_flip` are StegoMap (or None), the rest raw addresses or tensors
-    (tests: the error codes) -> the return code, unchecked."""
-    return int(load().stego_stitch_probe(_desc_ref(desc), _ref(code),
-                                         _ref(code_flip), _addr(lin_w), _addr(lin_b), _addr(centroids),
-                                         _addr(lin_out), _addr(clu_out), stream if stream is not None else None))
 
 
 def stitch_probe(code, code_flip, lin_w, lin_b, centroids, size, win, stride, lin_kind, clu_kind, alpha):
@@ -1447,13 +1125,6 @@ def stitch_probe(code, code_flip, lin_w, lin_b, centroids, size, win, stride, li
     return lo, co
 
 
-def window_gather_raw(layout, img, t0, n, out, out_flip, stream=None):
-    """stego_window_gather with every argument given: `img` is a StegoMap (or None), `out` / `out_flip` raw addresses or tensors ->
-    the return code, unchecked."""
-    return int(load().stego_window_gather(_desc_ref(layout), _ref(img),
-                                          int(t0), int(n), _addr(out), _addr(out_flip), stream if stream is not None else None))
-
-
 def window_gather(img, win, stride, t0, n, flip=False):
     """stego_window_gather: windows [t0, t0 + n) of the float32 image [3, H, W] (any strides) -> float32 [n, 3, win, win], and with
     `flip` also their horizontal mirror images: (windows, mirrored windows)."""
@@ -1464,7 +1135,7 @@ def window_gather(img, win, stride, t0, n, flip=False):
     dev = img.device
     layout = window_layout(H, W, win, stride)
     shape = (max(int(n), 0), 3, max(int(win), 0), max(int(win), 0))
-    ok = load().stego_window_gather(byref(layout), None, int(t0), int(n), None, None, None) == 1       # only the pointers are missing
+    ok = window_gather_raw(layout, None, t0, n, None, None) == 1       # only the pointers are missing
     out = torch.empty(shape if ok else (0,), dtype=torch.float32, device=dev)
     out_flip = torch.empty(shape if ok else (0,), dtype=torch.float32, device=dev) if flip else None
     with _on_device(dev):
@@ -1484,33 +1155,16 @@ def render_desc(B, H, W, n_lut=1, label_dtype=RENDER_I64, flags=RENDER_LABELS, a
     return d
 
 
-def image_range_workspace_bytes(desc):
-    """stego_image_range_workspace_bytes (host only); 0 for an invalid descriptor."""
-    return int(load().stego_image_range_workspace_bytes(byref(desc)))
-
-
-def image_range_raw(desc, image, rng, workspace, workspace_bytes, stream=None):
-    """stego_image_range with every argument given: `image` is a StegoMap (or None), the rest raw addresses or tensors -> the return
-    code, unchecked."""
-    return int(load().stego_image_range(_desc_ref(desc), _ref(image), _addr(rng), _addr(workspace), int(workspace_bytes),
-                                        stream if stream is not None else None))
-
-
-def render_raw(desc, image, labels, lut, rng, out, stream=None):
-    """stego_render with every argument given: `image` is a StegoMap (or None), the rest raw addresses or tensors -> the return code,
-    unchecked."""
-    return int(load().stego_render(_desc_ref(desc), _ref(image), _addr(labels), _addr(lut), _addr(rng), _addr(out),
-                                   stream if stream is not None else None))
+image_range_workspace_bytes = _bytes("stego_image_range_workspace_bytes")
+image_range_raw = _raw("stego_image_range")
+render_raw = _raw("stego_render")
 
 
 def image_range(desc, image):
     """stego_image_range of the float32 image [B, 3, H, W] (any strides) -> float32 [B, 2], (lo, hi) per image."""
     _require_dev(image)
     dev = image.device
-    need = image_range_workspace_bytes(desc)
-    if need == 0:
-        _check(image_range_raw(desc, None, None, None, 0))
-    ws = _empty_bytes(need, dev)
+    ws, need = _workspace(image_range_workspace_bytes, desc, dev, lambda: image_range_raw(desc, None, None, None, 0))
     rng = torch.empty((desc.B, 2), dtype=torch.float32, device=dev)
     with _on_device(dev):
         _check(image_range_raw(desc, _map(image), rng, ws, need, _stream()))
@@ -1531,34 +1185,14 @@ def pca_desc(B, C, h, w, H=1, W=1, joint=False, n_iter=PCA_DEFAULT_ITER, resize=
                         else int(joint), int(n_iter), int(resize), int(scale), int(out_strides[0]), int(out_strides[1]))
 
 
-def pca_workspace_bytes(desc):
-    """stego_pca_workspace_bytes (host only); 0 for an invalid descriptor."""
-    return int(load().stego_pca_workspace_bytes(byref(desc)))
-
-
-def pca_fit_raw(desc, fmap, mean, cov, basis, stats, workspace, workspace_bytes, stream=None):
-    """stego_pca_fit with every argument given: `fmap` is a StegoMap (or None), the rest raw addresses or tensors -> the return code,
-    unchecked."""
-    return int(load().stego_pca_fit(_desc_ref(desc), _ref(fmap), _addr(mean), _addr(cov), _addr(basis), _addr(stats), _addr(workspace),
-                                    int(workspace_bytes), stream if stream is not None else None))
-
-
-def pca_scores_raw(desc, fmap, mean, basis, scores, rng, workspace, workspace_bytes, stream=None):
-    """stego_pca_scores with every argument given -> the return code, unchecked."""
-    return int(load().stego_pca_scores(_desc_ref(desc), _ref(fmap), _addr(mean), _addr(basis), _addr(scores), _addr(rng),
-                                       _addr(workspace), int(workspace_bytes), stream if stream is not None else None))
-
-
-def pca_paint_raw(desc, scores, rng, out, stream=None):
-    """stego_pca_paint with every argument given -> the return code, unchecked."""
-    return int(load().stego_pca_paint(_desc_ref(desc), _addr(scores), _addr(rng), _addr(out), stream if stream is not None else None))
+pca_workspace_bytes = _bytes("stego_pca_workspace_bytes")
+pca_fit_raw = _raw("stego_pca_fit")
+pca_scores_raw = _raw("stego_pca_scores")
+pca_paint_raw = _raw("stego_pca_paint")
 
 
 def _pca_workspace(desc, dev):
-    need = pca_workspace_bytes(desc)
-    if need == 0:
-        _check(pca_paint_raw(desc, None, None, None))          # raises with the descriptor's own code
-    return _empty_bytes(need, dev), need
+    return _workspace(pca_workspace_bytes, desc, dev, lambda: pca_paint_raw(desc, None, None, None))
 
 
 def pca_fit(desc, fmap):
@@ -1598,13 +1232,10 @@ def pca_paint(desc, scores, rng, out):
 
 
 # ---- cluster refit (include/stego_kmeans.h; stego_amd.cluster_refit wraps them)
-def kmeans_desc(B, K, h, w, n):
-    return StegoKmeansDesc(int(B), int(K), int(h), int(w), int(n))
-
-
-def kmeans_workspace_bytes(desc):
-    """stego_kmeans_workspace_bytes (host only); 0 for an invalid descriptor."""
-    return int(load().stego_kmeans_workspace_bytes(byref(desc)))
+kmeans_desc = _desc(StegoKmeansDesc)
+kmeans_workspace_bytes = _bytes("stego_kmeans_workspace_bytes")
+kmeans_step_raw = _raw("stego_kmeans_step")
+kmeans_seed_raw = _raw("stego_kmeans_seed")      # (`u`: a host array of doubles)
 
 
 def kmeans_plan(desc):
@@ -1614,27 +1245,12 @@ def kmeans_plan(desc):
     return int(lds), int(wgs.value)
 
 
-def kmeans_step_raw(desc, codes, cin, cout, labels, counts, stats, workspace, workspace_bytes, stream=None):
-    """stego_kmeans_step with every argument given: `codes` is a StegoMap (or None), the rest raw addresses or tensors -> the return
-    code, unchecked."""
-    return int(load().stego_kmeans_step(_desc_ref(desc), _ref(codes), _addr(cin), _addr(cout), _addr(labels), _addr(counts), _addr(stats),
-                                        _addr(workspace), int(workspace_bytes), stream if stream is not None else None))
+def kmeans_workspace(desc, dev):
+    """(workspace tensor, its bytes) for kmeans_step / kmeans_seed calls with this descriptor."""
+    return _workspace(kmeans_workspace_bytes, desc, dev, lambda: kmeans_step_raw(desc, None, None, None, None, None, None, None, 0))
 
 
-def kmeans_seed_raw(desc, codes, u, centroids, picks, workspace, workspace_bytes, stream=None):
-    """stego_kmeans_seed with every argument given; `u` is a host address (a ctypes array of doubles), a raw address or None -> the
-    return code, unchecked."""
-    if isinstance(u, ctypes.Array):
-        u = ctypes.cast(u, c_void_p)
-    return int(load().stego_kmeans_seed(_desc_ref(desc), _ref(codes), u, _addr(centroids), _addr(picks), _addr(workspace),
-                                        int(workspace_bytes), stream if stream is not None else None))
-
-
-def _kmeans_workspace(desc, dev):
-    need = kmeans_workspace_bytes(desc)
-    if need == 0:
-        _check(kmeans_step_raw(desc, None, None, None, None, None, None, None, 0))          # raises with the descriptor's own code
-    return _empty_bytes(need, dev), need
+_kmeans_workspace = kmeans_workspace
 
 
 def kmeans_step(desc, codes, cin, cout=None, labels=None, counts=None, stats=None, workspace=None):
@@ -1643,7 +1259,7 @@ def kmeans_step(desc, codes, cin, cout=None, labels=None, counts=None, stats=Non
     workspace: what kmeans_workspace(desc, device) returned, for callers that step repeatedly.  -> (counts, stats)."""
     _require_dev(codes, cin, cout, labels, counts, stats)
     dev = codes.device
-    ws, need = workspace if workspace is not None else _kmeans_workspace(desc, dev)
+    ws, need = workspace if workspace is not None else kmeans_workspace(desc, dev)
     if counts is None:
         counts = torch.empty((desc.n,), dtype=torch.int64, device=dev)
     if stats is None:
@@ -1651,17 +1267,11 @@ def kmeans_step(desc, codes, cin, cout=None, labels=None, counts=None, stats=Non
     for name, t_, shape, dtype in (("centroids", cin, (desc.n, desc.K), torch.float32), ("out", cout, (desc.n, desc.K), torch.float32),
                                    ("labels", labels, (desc.B, desc.h, desc.w), torch.uint8), ("counts", counts, (desc.n,), torch.int64),
                                    ("stats", stats, (4,), torch.float64)):
-        if t_ is not None and (tuple(t_.shape) != shape or t_.dtype != dtype or not t_.is_contiguous()):
-            raise RuntimeError("kmeans_step: %s must be a contiguous %s tensor of shape %s, got %s %s"
-                               % (name, dtype, shape, t_.dtype, tuple(t_.shape)))
+        if t_ is not None:
+            _expect("kmeans_step", name, t_, dtype, shape)
     with _on_device(dev):
         _check(kmeans_step_raw(desc, _map(codes), cin, cout, labels, counts, stats, ws, need, _stream()))
     return counts, stats
-
-
-def kmeans_workspace(desc, dev):
-    """(workspace tensor, its bytes) for kmeans_step / kmeans_seed calls with this descriptor."""
-    return _kmeans_workspace(desc, dev)
 
 
 def kmeans_seed(desc, codes, u, workspace=None):
@@ -1669,7 +1279,7 @@ def kmeans_seed(desc, codes, u, workspace=None):
     [n]) on the codes' device, nothing synchronised."""
     _require_dev(codes)
     dev = codes.device
-    ws, need = workspace if workspace is not None else _kmeans_workspace(desc, dev)
+    ws, need = workspace if workspace is not None else kmeans_workspace(desc, dev)
     draws = (ctypes.c_double * desc.n)(*[float(v) for v in u])
     cent = torch.empty((desc.n, desc.K), dtype=torch.float32, device=dev)
     picks = torch.empty((desc.n,), dtype=torch.int64, device=dev)
@@ -1679,13 +1289,12 @@ def kmeans_seed(desc, codes, u, workspace=None):
 
 
 # ---- segments as objects (include/stego_regions.h; stego_amd.regions wraps them)
-def regions_desc(B, H, W, connectivity=4, label_dtype=REGIONS_I64):
-    return StegoRegionsDesc(int(B), int(H), int(W), int(connectivity), int(label_dtype))
-
-
-def regions_workspace_bytes(desc):
-    """stego_regions_workspace_bytes (host only); 0 for an invalid descriptor."""
-    return int(load().stego_regions_workspace_bytes(byref(desc)))
+regions_desc = _desc(StegoRegionsDesc, connectivity=4, label_dtype=REGIONS_I64)
+regions_workspace_bytes = _bytes("stego_regions_workspace_bytes")
+regions_label_raw = _raw("stego_regions_label")
+regions_table_raw = _raw("stego_regions_table")
+regions_votes_raw = _raw("stego_regions_votes")
+regions_relabel_raw = _raw("stego_regions_relabel")
 
 
 def regions_plan(desc):
@@ -1696,29 +1305,6 @@ def regions_plan(desc):
     return int(rc), int(tile.value), [(int(a), int(b)) for a, b in zip(lds, wgs)]
 
 
-def regions_label_raw(desc, labels, ids, n_regions, root, workspace, workspace_bytes, stream=None):
-    """stego_regions_label with every argument given (tensors, raw addresses or None) -> the return code, unchecked."""
-    return int(load().stego_regions_label(_desc_ref(desc), _addr(labels), _addr(ids), _addr(n_regions), _addr(root), _addr(workspace),
-                                          int(workspace_bytes), stream if stream is not None else None))
-
-
-def regions_table_raw(desc, labels, ids, row_offset, capacity, cols32, cols64, stream=None):
-    return int(load().stego_regions_table(_desc_ref(desc), _addr(labels), _addr(ids), _addr(row_offset), int(capacity), _addr(cols32),
-                                          _addr(cols64), stream if stream is not None else None))
-
-
-def regions_votes_raw(desc, labels, ids, row_offset, capacity, small_rank, lo, hi, n_labels, votes, stream=None):
-    return int(load().stego_regions_votes(_desc_ref(desc), _addr(labels), _addr(ids), _addr(row_offset), int(capacity), _addr(small_rank),
-                                          int(lo), int(hi), int(n_labels), _addr(votes), stream if stream is not None else None))
-
-
-def regions_relabel_raw(desc, labels_in, labels_out, ids, row_offset, capacity, small_rank, first, lo, hi, n_labels, votes, changed,
-                        stream=None):
-    return int(load().stego_regions_relabel(_desc_ref(desc), _addr(labels_in), _addr(labels_out), _addr(ids), _addr(row_offset),
-                                            int(capacity), _addr(small_rank), _addr(first), int(lo), int(hi), int(n_labels), _addr(votes),
-                                            _addr(changed), stream if stream is not None else None))
-
-
 def _regions_desc_of(labels, connectivity):
     if labels.dim() != 3 or labels.dtype not in REGIONS_DTYPES or not labels.is_contiguous():
         raise RuntimeError("regions: labels must be a contiguous int64, int32 or uint8 [B, H, W] tensor, got %s %s"
@@ -1727,24 +1313,16 @@ def _regions_desc_of(labels, connectivity):
     return regions_desc(B, H, W, connectivity, REGIONS_DTYPES[labels.dtype])
 
 
-def _regions_int32(name, t_, shape):
-    if t_.dtype != torch.int32 or tuple(t_.shape) != tuple(shape) or not t_.is_contiguous():
-        raise RuntimeError("regions: %s must be a contiguous int32 tensor of shape %s, got %s %s" % (name, tuple(shape), t_.dtype, tuple(t_.shape)))
-
-
 def regions_label(labels, connectivity=4):
     """stego_regions_label on torch's current stream, nothing synchronised -> (ids int32 [B, H, W], n_regions int32 [B], root int32
     [B, H, W])."""
     _require_dev(labels)
     desc = _regions_desc_of(labels, connectivity)
-    need = regions_workspace_bytes(desc)
-    if need == 0:
-        _check(regions_label_raw(desc, None, None, None, None, None, 0))             # raises with the descriptor's own code
     dev = labels.device
+    ws, need = _workspace(regions_workspace_bytes, desc, dev, lambda: _call("stego_regions_plan", desc, None, None, None))
     ids = torch.empty(labels.shape, dtype=torch.int32, device=dev)
     root = torch.empty(labels.shape, dtype=torch.int32, device=dev)
     n_regions = torch.empty((labels.shape[0],), dtype=torch.int32, device=dev)
-    ws = _empty_bytes(need, dev)
     with _on_device(dev):
         _check(regions_label_raw(desc, labels, ids, n_regions, root, ws, need, _stream()))
     return ids, n_regions, root
@@ -1755,9 +1333,8 @@ def regions_table(labels, ids, row_offset, capacity):
     row_offset: int64 [B], the first row of every image."""
     _require_dev(labels, ids, row_offset)
     desc = _regions_desc_of(labels, 4)
-    _regions_int32("ids", ids, labels.shape)
-    if row_offset.dtype != torch.int64 or tuple(row_offset.shape) != (labels.shape[0],) or not row_offset.is_contiguous():
-        raise RuntimeError("regions: row_offset must be a contiguous int64 [B] tensor")
+    _expect("regions", "ids", ids, torch.int32, labels.shape)
+    _expect("regions", "row_offset", row_offset, torch.int64, (labels.shape[0],))
     dev = labels.device
     cols32 = torch.empty((len(REGIONS_COLS32), int(capacity)), dtype=torch.int32, device=dev)
     cols64 = torch.empty((len(REGIONS_COLS64), int(capacity)), dtype=torch.int64, device=dev)
@@ -1770,8 +1347,8 @@ def regions_votes(labels, ids, row_offset, small_rank, lo, hi, n_labels, votes=N
     """stego_regions_votes -> votes int32 [hi - lo, n_labels] (reset by the call)."""
     _require_dev(labels, ids, row_offset, small_rank, votes)
     desc = _regions_desc_of(labels, 4)
-    _regions_int32("ids", ids, labels.shape)
-    _regions_int32("small_rank", small_rank, (small_rank.numel(),))
+    _expect("regions", "ids", ids, torch.int32, labels.shape)
+    _expect("regions", "small_rank", small_rank, torch.int32, (small_rank.numel(),))
     rows = max(int(hi) - int(lo), 0)
     if votes is None:
         votes = torch.empty((rows, max(int(n_labels), 0)), dtype=torch.int32, device=labels.device)
@@ -1789,10 +1366,10 @@ def regions_relabel(labels_in, labels_out, ids, row_offset, small_rank, first, l
     if labels_out.dtype != labels_in.dtype or labels_out.shape != labels_in.shape or not labels_out.is_contiguous() or \
             labels_out.data_ptr() == labels_in.data_ptr():
         raise RuntimeError("regions: labels_out must be another contiguous tensor of labels_in's dtype and shape")
-    _regions_int32("ids", ids, labels_in.shape)
-    _regions_int32("small_rank", small_rank, (small_rank.numel(),))
-    _regions_int32("first", first, (small_rank.numel(),))
-    _regions_int32("changed", changed, (1,))
+    _expect("regions", "ids", ids, torch.int32, labels_in.shape)
+    _expect("regions", "small_rank", small_rank, torch.int32, (small_rank.numel(),))
+    _expect("regions", "first", first, torch.int32, (small_rank.numel(),))
+    _expect("regions", "changed", changed, torch.int32, (1,))
     if votes.dtype != torch.int32 or votes.numel() < max(int(hi) - int(lo), 0) * int(n_labels) or not votes.is_contiguous():
         raise RuntimeError("regions: votes must be a contiguous int32 tensor of at least (hi - lo) * n_labels elements")
     with _on_device(labels_in.device):
@@ -1801,13 +1378,9 @@ def regions_relabel(labels_in, labels_out, ids, row_offset, small_rank, first, l
 
 
 # ---- region descriptors (include/stego_region_pool.h; stego_amd.region_descriptors wraps them)
-def region_pool_desc(B, C, h, w, H, W, rows):
-    return StegoRegionPoolDesc(int(B), int(C), int(h), int(w), int(H), int(W), int(rows))
-
-
-def region_pool_workspace_bytes(desc):
-    """stego_region_pool_workspace_bytes (host only); 0 for an invalid descriptor."""
-    return int(load().stego_region_pool_workspace_bytes(byref(desc)))
+region_pool_desc = _desc(StegoRegionPoolDesc)
+region_pool_workspace_bytes = _bytes("stego_region_pool_workspace_bytes")
+region_pool_raw = _raw("stego_region_pool")
 
 
 def region_pool_plan(desc):
@@ -1819,31 +1392,19 @@ def region_pool_plan(desc):
     return int(rc), int(seg.value), int(cb.value), [(int(a), int(b)) for a, b in zip(lds, wgs)]
 
 
-def region_pool_raw(desc, map_, ids, row_offset, area, capacity, lo, hi, out, workspace, workspace_bytes, stream=None):
-    """stego_region_pool with every argument given (a StegoMap or None; tensors, raw addresses or None) -> the return code, unchecked."""
-    return int(load().stego_region_pool(_desc_ref(desc), _ref(map_), _addr(ids), _addr(row_offset), _addr(area), int(capacity), int(lo),
-                                        int(hi), _addr(out), _addr(workspace), int(workspace_bytes),
-                                        stream if stream is not None else None))
-
-
 def region_pool(maps, ids, row_offset, area, lo, hi, out=None, workspace=None):
     """stego_region_pool on torch's current stream, nothing synchronised: maps float32 [B, C, h, w] (any strides), ids int32 [B, H, W],
     row_offset int64 [B], area int32 [capacity] -> float32 [hi - lo, C], the descriptors of the table rows [lo, hi).  `out` and
     `workspace` (uint8, from an earlier call of at least as many rows) are reused when given."""
     _require_dev(maps, ids, row_offset, area, out, workspace)
     m = _map(maps)
-    if ids.dim() != 3 or ids.dtype != torch.int32 or not ids.is_contiguous() or ids.shape[0] != maps.shape[0]:
-        raise RuntimeError("region_pool: ids must be a contiguous int32 [%d, H, W] tensor, got %s %s" % (maps.shape[0], ids.dtype, tuple(ids.shape)))
-    if row_offset.dtype != torch.int64 or tuple(row_offset.shape) != (maps.shape[0],) or not row_offset.is_contiguous():
-        raise RuntimeError("region_pool: row_offset must be a contiguous int64 [B] tensor")
-    if area.dtype != torch.int32 or area.dim() != 1 or not area.is_contiguous():
-        raise RuntimeError("region_pool: area must be a contiguous int32 [capacity] tensor")
+    _expect("region_pool", "ids", ids, torch.int32, (maps.shape[0], None, None))
+    _expect("region_pool", "row_offset", row_offset, torch.int64, (maps.shape[0],))
+    _expect("region_pool", "area", area, torch.int32, (None,))
     B, C, h, w = maps.shape
     rows = max(int(hi) - int(lo), 0)
     desc = region_pool_desc(B, C, h, w, ids.shape[1], ids.shape[2], rows)
-    need = region_pool_workspace_bytes(desc)
-    if need == 0:
-        _check(region_pool_raw(desc, None, None, None, None, 0, 0, 0, None, None, 0))      # raises with the descriptor's own code
+    need = _workspace_need(region_pool_workspace_bytes, desc, lambda: _call("stego_region_pool_plan", desc, None, None, None, None))
     dev = maps.device
     if out is None:
         out = torch.empty((rows, C), dtype=torch.float32, device=dev)
@@ -1857,13 +1418,10 @@ def region_pool(maps, ids, row_offset, area, lo, hi, out=None, workspace=None):
 
 
 # ---- device-side confusion matrices (include/stego_confusion.h; stego_amd.metrics wraps them for the trainer and evaluate())
-def probe_confusion_desc(B, K, h, w, H, W, n_lin, n_clu, lin_on, clu_on, alpha, n_classes):
-    return StegoProbeConfusionDesc(int(B), int(K), int(h), int(w), int(H), int(W), int(n_lin), int(n_clu), int(lin_on), int(clu_on),
-                                   float(alpha), int(n_classes))
-
-
-def confusion_desc(B, n, H, W, n_classes, pred_kind):
-    return StegoConfusionDesc(int(B), int(n), int(H), int(W), int(n_classes), int(pred_kind))
+probe_confusion_desc = _desc(StegoProbeConfusionDesc)
+confusion_desc = _desc(StegoConfusionDesc)
+probe_confusion_raw = _raw("stego_probe_confusion")
+confusion_raw = _raw("stego_confusion")
 
 
 def probe_confusion_plan(desc):
@@ -1872,15 +1430,6 @@ def probe_confusion_plan(desc):
     ty, tx = c_int32(0), c_int32(0)
     n = load().stego_probe_confusion_plan(byref(desc), byref(ty), byref(tx))
     return int(n), ty.value, tx.value
-
-
-def probe_confusion_raw(desc, code, code_flip, lin_w, lin_b, centroids, labels, lin_counts, clu_counts, stream=None):
-    """stego_probe_confusion with every argument given: `code` / `code_flip` are StegoMap (or None), the rest raw addresses or
-    tensors (tests: the error codes) -> the return code, unchecked."""
-    return int(load().stego_probe_confusion(_desc_ref(desc), _ref(code),
-                                            _ref(code_flip), _addr(lin_w), _addr(lin_b),
-                                            _addr(centroids), _addr(labels), _addr(lin_counts), _addr(clu_counts),
-                                            stream if stream is not None else None))
 
 
 def _counts_ok(counts, n, n_classes, name):
@@ -1924,12 +1473,6 @@ def probe_confusion(code, code_flip, lin_w, lin_b, centroids, labels, lin_counts
     with _on_device(code.device):
         _check(probe_confusion_raw(desc, _map(code), _map(code_flip) if code_flip is not None else None, lw, lb, ce, labels,
                                    lin_counts, clu_counts, _stream()))
-
-
-def confusion_raw(desc, pred, labels, counts, stream=None):
-    """stego_confusion with raw addresses or tensors (tests: the error codes) -> the return code, unchecked."""
-    return int(load().stego_confusion(_desc_ref(desc), _addr(pred), _addr(labels), _addr(counts),
-                                      stream if stream is not None else None))
 
 
 def confusion(pred, labels, counts, kind):
@@ -1978,19 +1521,11 @@ def adam_desc(n_segments, groups, zero_grads, grad_elems, state_elems, n_groups=
 def adam_plan(desc, segments_host):
     """stego_adam_plan (host only) -> (return code, grid, chunk, n_chunks); the last three are 0 when the code is not 0."""
     grid, chunk, n = c_int32(0), c_int32(0), c_int64(0)
-    rc = load().stego_adam_plan(_desc_ref(desc),
-                                ctypes.addressof(segments_host) if segments_host is not None else None, byref(grid), byref(chunk),
-                                byref(n))
-    return int(rc), grid.value, chunk.value, n.value
+    rc = _call("stego_adam_plan", desc, segments_host, byref(grid), byref(chunk), byref(n))
+    return rc, grid.value, chunk.value, n.value
 
 
-def adam_step_raw(desc, segments_host, segments, grads, exp_avg, exp_avg_sq, steps, ticket, stream=None):
-    """stego_adam_step with every argument given: `segments_host` a ctypes array (or None), the rest raw addresses or tensors (tests:
-    the error codes) -> the return code, unchecked."""
-    return int(load().stego_adam_step(_desc_ref(desc),
-                                      ctypes.addressof(segments_host) if segments_host is not None else None, _addr(segments),
-                                      _addr(grads), _addr(exp_avg), _addr(exp_avg_sq), _addr(steps), _addr(ticket),
-                                      stream if stream is not None else None))
+adam_step_raw = _raw("stego_adam_step")       # (`segments_host`: the ctypes array of adam_segments, or None)
 
 
 def adam_step(desc, segments_host, segments, grads, exp_avg, exp_avg_sq, steps, ticket):
@@ -2013,7 +1548,7 @@ def stats_desc(counts, n_scalars, with_hist, ring_slots, n_tensors=None):
 def step_stats_plan(desc):
     """stego_step_stats_plan (host only) -> (return code, {field: value}); the dict is empty when the code is not 0."""
     plan = StegoStatsPlan()
-    rc = int(load().stego_step_stats_plan(_desc_ref(desc), byref(plan)))
+    rc = _call("stego_step_stats_plan", desc, plan)
     return rc, ({name: int(getattr(plan, name)) for name in STATS_PLAN_FIELDS} if rc == 0 else {})
 
 
@@ -2035,8 +1570,7 @@ def step_stats_raw(desc, tensors, scalars, ring, state, workspace, stream=None):
         for i, x in enumerate(xs):
             arr[i] = _addr(x)
         return arr
-    return int(load().stego_step_stats(_desc_ref(desc), table(tensors), table(scalars), _addr(ring), _addr(state), _addr(workspace),
-                                       stream if stream is not None else None))
+    return _call("stego_step_stats", desc, table(tensors), table(scalars), ring, state, workspace, stream)
 
 
 def pointer_table(n):
@@ -2060,8 +1594,9 @@ def step_stats(desc, tensors, scalars, ring, state, workspace):
 
 
 # ---- fused training tail of the two probes (include/stego_probe_train.h; stego_amd.probe_train wraps it for the trainer)
-def probe_train_desc(B, K, h, w, H, W, n_lin, n_clu):
-    return StegoProbeTrainDesc(int(B), int(K), int(h), int(w), int(H), int(W), int(n_lin), int(n_clu))
+probe_train_desc = _desc(StegoProbeTrainDesc)
+probe_train_workspace_bytes = _bytes("stego_probe_train_workspace_bytes")
+probe_train_raw = _raw("stego_probe_train")
 
 
 def probe_train_plan(desc):
@@ -2069,19 +1604,6 @@ def probe_train_plan(desc):
     wgs = c_int32(0)
     n = load().stego_probe_train_plan(byref(desc), byref(wgs))
     return int(n), wgs.value
-
-
-def probe_train_workspace_bytes(desc):
-    return int(load().stego_probe_train_workspace_bytes(byref(desc)))
-
-
-def probe_train_raw(desc, code, label, lin_w, lin_b, clusters, losses, n_valid, d_lin_w, d_lin_b, d_clusters, workspace, workspace_bytes,
-                    stream=None):
-    """stego_probe_train with every argument given: `code` is a StegoMap (or None), the rest raw addresses or tensors (tests: the error
-    codes) -> the return code, unchecked."""
-    return int(load().stego_probe_train(byref(desc), _ref(code), _addr(label), _addr(lin_w), _addr(lin_b),
-                                        _addr(clusters), _addr(losses), _addr(n_valid), _addr(d_lin_w), _addr(d_lin_b), _addr(d_clusters),
-                                        _addr(workspace), int(workspace_bytes), stream if stream is not None else None))
 
 
 def probe_train(code, label, lin_w, lin_b, clusters):
@@ -2114,19 +1636,17 @@ def probe_train(code, label, lin_w, lin_b, clusters):
     d_lin_w = torch.empty(n_lin, K, dtype=torch.float32, device=dev) if lin else None
     d_lin_b = torch.empty(n_lin, dtype=torch.float32, device=dev) if lin else None
     d_clusters = torch.empty(n_clu, K, dtype=torch.float32, device=dev) if clu else None
-    n = probe_train_workspace_bytes(desc)
-    if n == 0:
-        _check(probe_train_raw(desc, _map(code), label, lin_w, lin_b, clusters, losses, n_valid, d_lin_w, d_lin_b, d_clusters, None, 0))
-    ws = _empty_bytes(n, dev)
+    mc = _map(code)
+    ws, n = _workspace(probe_train_workspace_bytes, desc, dev, lambda: probe_train_raw(
+        desc, mc, label, lin_w, lin_b, clusters, losses, n_valid, d_lin_w, d_lin_b, d_clusters, None, 0))
     with _on_device(dev):
-        _check(probe_train_raw(desc, _map(code), label, lin_w, lin_b, clusters, losses, n_valid, d_lin_w, d_lin_b, d_clusters, ws, n,
-                               _stream()))
+        _check(probe_train_raw(desc, mc, label, lin_w, lin_b, clusters, losses, n_valid, d_lin_w, d_lin_b, d_clusters, ws, n, _stream()))
     return losses, n_valid, d_lin_w, d_lin_b, d_clusters
 
 
 # ---- label co-occurrence PR histogram of feature correspondences (include/stego_pr.h; stego_amd.correspondence_pr wraps it)
-def pr_desc(B, C, h, w, HL, WL, N1, N2, n_bins, n_classes, flags=0):
-    return StegoPrDesc(int(B), int(C), int(h), int(w), int(HL), int(WL), int(N1), int(N2), int(n_bins), int(n_classes), int(flags))
+pr_desc = _desc(StegoPrDesc, flags=0)
+pr_accumulate_raw = _raw("stego_pr_accumulate")
 
 
 def pr_plan(desc):
@@ -2134,14 +1654,6 @@ def pr_plan(desc):
     t1, t2 = c_int32(0), c_int32(0)
     n = load().stego_pr_plan(byref(desc), byref(t1), byref(t2))
     return int(n), t1.value, t2.value
-
-
-def pr_accumulate_raw(desc, a, b, labels_a, labels_b, index_b, coords1, coords2, hist, stream=None):
-    """stego_pr_accumulate with every argument given: `a` / `b` are StegoMap (or None), the rest raw addresses or tensors (tests: the
-    error codes) -> the return code, unchecked."""
-    return int(load().stego_pr_accumulate(byref(desc), _ref(a), _ref(b),
-                                          _addr(labels_a), _addr(labels_b), _addr(index_b), _addr(coords1), _addr(coords2), _addr(hist),
-                                          stream if stream is not None else None))
 
 
 def pr_accumulate(a, b, labels_a, labels_b, coords1, coords2, hist, n_classes, index_b=None, normalize=True, skip_unlabeled=False):
@@ -2172,12 +1684,9 @@ def pr_accumulate(a, b, labels_a, labels_b, coords1, coords2, hist, n_classes, i
 
 
 # ---- query-point correspondence heatmaps (include/stego_heat.h; stego_amd.correspondence_heatmaps wraps it)
-def heat_desc(B, C, hs, ws, h, w, N, H, W, flags=0):
-    return StegoHeatDesc(int(B), int(C), int(hs), int(ws), int(h), int(w), int(N), int(H), int(W), int(flags))
-
-
-def heat_workspace_bytes(desc):
-    return int(load().stego_heat_workspace_bytes(byref(desc)))
+heat_desc = _desc(StegoHeatDesc, flags=0)
+heat_workspace_bytes = _bytes("stego_heat_workspace_bytes")
+corr_heatmaps_raw = _raw("stego_corr_heatmaps")
 
 
 def heat_plan(desc):
@@ -2200,14 +1709,6 @@ def heat_workspace_views(desc, ws):
             ws[o2:o3].view(torch.float32).view(desc.B, desc.N, nch), ws[o3:o3 + rows * nch * 4].view(torch.int32).view(desc.B, desc.N, nch))
 
 
-def corr_heatmaps_raw(desc, src, tgt, index_t, points, heat, peak, best, workspace, workspace_bytes, stream=None):
-    """stego_corr_heatmaps with every argument given: `src` / `tgt` are StegoMap (or None), the rest raw addresses or tensors (tests:
-    the error codes) -> the return code, unchecked."""
-    return int(load().stego_corr_heatmaps(byref(desc), _ref(src), _ref(tgt),
-                                          _addr(index_t), _addr(points), _addr(heat), _addr(peak), _addr(best), _addr(workspace),
-                                          int(workspace_bytes), stream if stream is not None else None))
-
-
 def corr_heatmaps(src, tgt, points, size, center=True, clamp=True, index_t=None, want_best=False, keep_workspace=False):
     """stego_corr_heatmaps: src float32 [B, C, hs, ws], tgt float32 [B, C, h, w] (any strides), points [B, N, 2] or [B, N, 1, 2] as
     (x, y) in [-1, 1], index_t int64 [B] or None, all on one HIP device -> heat float32 [B, N, H, W] for size = (H, W); with want_best
@@ -2228,15 +1729,13 @@ def corr_heatmaps(src, tgt, points, size, center=True, clamp=True, index_t=None,
             raise ValueError("index_t has %d entries for %d images" % (index_t.numel(), B))
     desc = heat_desc(B, C, hs, ws_, h, w, N, H, W, (0 if center else HEAT_NO_CENTER) | (0 if clamp else HEAT_NO_CLAMP))
     dev = src.device
-    n = heat_workspace_bytes(desc)
-    if n == 0:
-        _check(corr_heatmaps_raw(desc, _map(src), _map(tgt), index_t, pts, 16, None, None, None, 0))      # raises with the descriptor's code
+    ms, mt = _map(src), _map(tgt)
+    ws, n = _workspace(heat_workspace_bytes, desc, dev, lambda: corr_heatmaps_raw(desc, ms, mt, index_t, pts, 16, None, None, None, 0))
     heat = torch.empty(B, N, H, W, dtype=torch.float32, device=dev)
     peak = torch.empty(B, N, dtype=torch.float32, device=dev) if want_best else None
     best = torch.empty(B, N, 2, dtype=torch.float32, device=dev) if want_best else None
-    ws = _empty_bytes(n, dev)
     with _on_device(dev):
-        _check(corr_heatmaps_raw(desc, _map(src), _map(tgt), index_t, pts, heat, peak, best, ws, n, _stream()))
+        _check(corr_heatmaps_raw(desc, ms, mt, index_t, pts, heat, peak, best, ws, n, _stream()))
     out = (heat, peak, best) if want_best else heat
     if keep_workspace:
         return out, desc, ws
@@ -2244,26 +1743,14 @@ def corr_heatmaps(src, tgt, points, size, center=True, clamp=True, index_t=None,
 
 
 # ---- fused ContrastiveCRFLoss, forward and backward (include/stego_crf_loss.h; stego_amd.crf_loss wraps it for the trainer)
-def crf_loss_desc(B, K, G, h, w, hg, wg, H, W, N, alpha, beta, gamma, w1, w2, shift, flags=CRFLOSS_NORMALIZE):
-    return StegoCrfLossDesc(int(B), int(K), int(G), int(h), int(w), int(hg), int(wg), int(H), int(W), int(N), float(alpha), float(beta),
-                            float(gamma), float(w1), float(w2), float(shift), int(flags))
-
-
-def crf_loss_workspace_bytes(desc):
-    return int(load().stego_crf_loss_workspace_bytes(byref(desc)))
+crf_loss_desc = _desc(StegoCrfLossDesc, flags=CRFLOSS_NORMALIZE)
+crf_loss_workspace_bytes = _bytes("stego_crf_loss_workspace_bytes")
+crf_loss_raw = _raw("stego_crf_loss")
 
 
 def crf_loss_plan(desc):
     """stego_crf_loss_plan (host only) -> (return code, [(LDS bytes, workgroups) of the prepare, pairs and finish launch])."""
-    return _launch_plan(load().stego_crf_loss_plan, desc, CRFLOSS_LAUNCHES)
-
-
-def crf_loss_raw(desc, guidance, code, coords, loss, per_image, d_code, workspace, workspace_bytes, stream=None):
-    """stego_crf_loss with every argument given: `guidance`, `code` and `d_code` are StegoMap (or None), the rest raw addresses or
-    tensors (tests: the error codes) -> the return code, unchecked."""
-    return int(load().stego_crf_loss(_desc_ref(desc), _ref(guidance), _ref(code), _addr(coords), _addr(loss),
-                                     _addr(per_image), _ref(d_code), _addr(workspace), int(workspace_bytes),
-                                     stream if stream is not None else None))
+    return _launch_plan("stego_crf_loss_plan", desc, CRFLOSS_LAUNCHES)
 
 
 def crf_loss(guidance, code, coords, size, params, normalize=True, need_grad=True, want_per_image=True, d_code_like=None):
@@ -2281,50 +1768,37 @@ def crf_loss(guidance, code, coords, size, params, normalize=True, need_grad=Tru
     G, hg, wg = guidance.shape[1:]
     coords = _dense(coords, torch.int64)
     dev = code.device
-    desc = crf_loss_desc(B, K, G, h, w, hg, wg, size[0], size[1], coords.shape[1], *params,
-                         flags=CRFLOSS_NORMALIZE if normalize else 0)
-    n = crf_loss_workspace_bytes(desc)
-    if n == 0:
-        _check(crf_loss_raw(desc, _map(guidance), _map(code), coords, 16, None, None, 16, 0))       # raises with the descriptor's code
+    desc = crf_loss_desc(B, K, G, h, w, hg, wg, size[0], size[1], coords.shape[1], *params, CRFLOSS_NORMALIZE if normalize else 0)
+    mg, mc = _map(guidance), _map(code)
+    ws, n = _workspace(crf_loss_workspace_bytes, desc, dev, lambda: _call("stego_crf_loss_plan", desc, None, None))
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     per_image = torch.empty(B, dtype=torch.float32, device=dev) if want_per_image else None
     d_code = torch.empty_like(code if d_code_like is None else d_code_like, dtype=torch.float32) if need_grad else None
-    ws = _empty_bytes(n, dev)
     with _on_device(dev):
-        _check(crf_loss_raw(desc, _map(guidance), _map(code), coords, loss, per_image, _map(d_code) if need_grad else None, ws, n,
-                            _stream()))
+        _check(crf_loss_raw(desc, mg, mc, coords, loss, per_image, _map(d_code) if need_grad else None, ws, n, _stream()))
     return loss, per_image, d_code
 
 
 # ---- device-side augmented views and the fused aug-alignment loss (include/stego_aug.h; stego_amd.augment wraps them for the trainer)
-def aug_desc(B, H, W, R):
-    return StegoAugDesc(int(B), int(H), int(W), int(R))
+aug_desc = _desc(StegoAugDesc)
+augment_workspace_bytes = _bytes("stego_augment_workspace_bytes")
+augment_raw = _raw("stego_augment")       # (`params_host`: a ctypes array of StegoAugParams, a raw address or None)
+aug_align_desc = _desc(StegoAugAlignDesc)
+aug_align_workspace_bytes = _bytes("stego_aug_align_workspace_bytes")
+aug_align_raw = _raw("stego_aug_align")
 
 
 def aug_check_params(desc, records):
     """stego_augment_check_params (host only): `records` a ctypes array of StegoAugParams (or None) ->
     (return code, index of the first bad record or -1, whether a record applies contrast)."""
     bad, contrast = c_int64(-1), c_int32(0)
-    rc = load().stego_augment_check_params(_desc_ref(desc),
-                                           ctypes.addressof(records) if records is not None else None, byref(bad), byref(contrast))
-    return int(rc), int(bad.value), bool(contrast.value)
-
-
-def augment_workspace_bytes(desc):
-    return int(load().stego_augment_workspace_bytes(byref(desc)))
+    rc = _call("stego_augment_check_params", desc, records, byref(bad), byref(contrast))
+    return rc, int(bad.value), bool(contrast.value)
 
 
 def augment_plan(desc):
     """stego_augment_plan (host only) -> (return code, [(LDS bytes, workgroups) of the mean and the apply launch])."""
-    return _launch_plan(load().stego_augment_plan, desc, AUG_LAUNCHES)
-
-
-def augment_raw(desc, img, params_host, params, img_aug, coord_aug, workspace, workspace_bytes, stream=None):
-    """stego_augment with every argument given: `img` a StegoMap (or None), `params_host` a ctypes array of StegoAugParams, a raw
-    address or None, the rest raw addresses or tensors (tests: the error codes) -> the return code, unchecked."""
-    host = ctypes.addressof(params_host) if isinstance(params_host, ctypes.Array) else params_host
-    return int(load().stego_augment(_desc_ref(desc), _ref(img), host, _addr(params), _addr(img_aug),
-                                    _addr(coord_aug), _addr(workspace), int(workspace_bytes), stream if stream is not None else None))
+    return _launch_plan("stego_augment_plan", desc, AUG_LAUNCHES)
 
 
 def aug_table(records, dev):
@@ -2345,38 +1819,20 @@ def augment(img, records, R, table=None):
         raise ValueError("augment: %d parameter records for %d images" % (len(records), B))
     dev = img.device
     desc = aug_desc(B, H, W, R)
-    n = augment_workspace_bytes(desc)
-    if n == 0:
-        _check(augment_raw(desc, _map(img), records, 16, 16, 16, 16, 0))          # raises with the descriptor's code
+    m = _map(img)
+    ws, n = _workspace(augment_workspace_bytes, desc, dev, lambda: _call("stego_augment_plan", desc, None, None))
     img_aug = torch.empty(B, 3, R, R, dtype=torch.float32, device=dev)
     coord_aug = torch.empty(B, R, R, 2, dtype=torch.float32, device=dev)
-    ws = _empty_bytes(n, dev)
     with _on_device(dev):
         if table is None:
             table = aug_table(records, dev)
-        _check(augment_raw(desc, _map(img), records, table, img_aug, coord_aug, ws, n, _stream()))
+        _check(augment_raw(desc, m, records, table, img_aug, coord_aug, ws, n, _stream()))
     return img_aug, coord_aug
-
-
-def aug_align_desc(B, K, h, w, S, Rh, Rw):
-    return StegoAugAlignDesc(int(B), int(K), int(h), int(w), int(S), int(Rh), int(Rw))
-
-
-def aug_align_workspace_bytes(desc):
-    return int(load().stego_aug_align_workspace_bytes(byref(desc)))
 
 
 def aug_align_plan(desc):
     """stego_aug_align_plan (host only) -> (return code, [(LDS bytes, workgroups) of the pixels and the finish launch])."""
-    return _launch_plan(load().stego_aug_align_plan, desc, AUGALIGN_LAUNCHES)
-
-
-def aug_align_raw(desc, code, code_aug, coord, loss, d_code, d_code_aug, workspace, workspace_bytes, stream=None):
-    """stego_aug_align with every argument given: the four maps are StegoMap (or None), the rest raw addresses or tensors (tests: the
-    error codes) -> the return code, unchecked."""
-    return int(load().stego_aug_align(_desc_ref(desc), _ref(code), _ref(code_aug), _addr(coord), _addr(loss),
-                                      _ref(d_code), _ref(d_code_aug), _addr(workspace), int(workspace_bytes),
-                                      stream if stream is not None else None))
+    return _launch_plan("stego_aug_align_plan", desc, AUGALIGN_LAUNCHES)
 
 
 def aug_align(code, code_aug, coord, need_code=True, need_code_aug=True):
@@ -2393,39 +1849,26 @@ def aug_align(code, code_aug, coord, need_code=True, need_code_aug=True):
     coord = _dense(coord, torch.float32)
     dev = code.device
     desc = aug_align_desc(B, K, h, w, code_aug.shape[2], coord.shape[1], coord.shape[2])
-    n = aug_align_workspace_bytes(desc)
-    if n == 0:
-        _check(aug_align_raw(desc, _map(code), _map(code_aug), coord, 16, None, None, 16, 0))       # raises with the descriptor's code
+    mc, ma = _map(code), _map(code_aug)
+    ws, n = _workspace(aug_align_workspace_bytes, desc, dev, lambda: _call("stego_aug_align_plan", desc, None, None))
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     d_code = torch.empty_like(code) if need_code else None
     d_code_aug = torch.empty_like(code_aug) if need_code_aug else None
-    ws = _empty_bytes(n, dev)
     with _on_device(dev):
-        _check(aug_align_raw(desc, _map(code), _map(code_aug), coord, loss, _map(d_code) if need_code else None,
+        _check(aug_align_raw(desc, mc, ma, coord, loss, _map(d_code) if need_code else None,
                              _map(d_code_aug) if need_code_aug else None, ws, n, _stream()))
     return loss, d_code, d_code_aug
 
 
 # ---- fused reconstruction loss, forward and backward (include/stego_rec.h; stego_amd.rec_loss wraps it for the trainer)
-def rec_desc(B, K, C, h, w):
-    return StegoRecDesc(int(B), int(K), int(C), int(h), int(w))
-
-
-def rec_loss_workspace_bytes(desc):
-    return int(load().stego_rec_loss_workspace_bytes(byref(desc)))
+rec_desc = _desc(StegoRecDesc)
+rec_loss_workspace_bytes = _bytes("stego_rec_loss_workspace_bytes")
+rec_loss_raw = _raw("stego_rec_loss")
 
 
 def rec_loss_plan(desc):
     """stego_rec_loss_plan (host only) -> (return code, [(LDS bytes, workgroups) of the tiles and the finish launch])."""
-    return _launch_plan(load().stego_rec_loss_plan, desc, REC_LAUNCHES)
-
-
-def rec_loss_raw(desc, code, feats, weight, bias, loss, d_code, d_weight, d_bias, workspace, workspace_bytes, stream=None):
-    """stego_rec_loss with every argument given: `code`, `feats` and `d_code` are StegoMap (or None), the rest raw addresses or
-    tensors (tests: the error codes) -> the return code, unchecked."""
-    return int(load().stego_rec_loss(_desc_ref(desc), _ref(code), _ref(feats), _addr(weight), _addr(bias),
-                                     _addr(loss), _ref(d_code), _addr(d_weight), _addr(d_bias), _addr(workspace), int(workspace_bytes),
-                                     stream if stream is not None else None))
+    return _launch_plan("stego_rec_loss_plan", desc, REC_LAUNCHES)
 
 
 def rec_loss(code, feats, weight, bias, need_code=True, need_weight=True, need_bias=True):
@@ -2443,15 +1886,12 @@ def rec_loss(code, feats, weight, bias, need_code=True, need_weight=True, need_b
     weight, bias = _dense(weight, torch.float32), _dense(bias, torch.float32)
     dev = code.device
     desc = rec_desc(B, K, C, h, w)
-    n = rec_loss_workspace_bytes(desc)
-    if n == 0:
-        _check(rec_loss_raw(desc, _map(code), _map(feats), weight, bias, 16, None, None, None, 16, 0))       # raises with the descriptor's code
+    mc, mf = _map(code), _map(feats)
+    ws, n = _workspace(rec_loss_workspace_bytes, desc, dev, lambda: _call("stego_rec_loss_plan", desc, None, None))
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     d_code = torch.empty_like(code) if need_code else None
     d_weight = torch.empty_like(weight) if need_weight else None
     d_bias = torch.empty_like(bias) if need_bias else None
-    ws = _empty_bytes(n, dev)
     with _on_device(dev):
-        _check(rec_loss_raw(desc, _map(code), _map(feats), weight, bias, loss, _map(d_code) if need_code else None, d_weight, d_bias,
-                            ws, n, _stream()))
+        _check(rec_loss_raw(desc, mc, mf, weight, bias, loss, _map(d_code) if need_code else None, d_weight, d_bias, ws, n, _stream()))
     return loss, d_code, d_weight, d_bias
